@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
 """env-steps/s of the fused VecTask.step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--task Ant] [--num-envs 65536]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--task Ant] [--num-envs 65536] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline needs: make() the envs, W warm-up steps, K timed steps, the outputs of the
+last timed step to DIR when --dump-outputs is given, and the JSON line (value, ms_per_step, and the roofline figures
+that come out of the timed launches themselves).  --full adds everything that takes runs of its own: the HIP-event
+pass (event_ms), the steady-state sample, `strong_scaling`, `cpu_baseline` and `baseline_config0`.
 
 One "step" = one VecTask.step of every env on every rank (controlFrequencyInv=1,
 2 physics substeps), random U(-1,1) actions generated on device before the timed
 region, inputs resident in HBM.  Envs are independent, so ranks shard them
-(weak scaling: --num-envs per GPU; the only collective is the obs/rew/reset gather to rank 0, timed).  The same
-line carries `strong_scaling`: BASELINE.json's fixed-total configs (MA-Ant 65,536 envs, ShadowHand 32,768, and Ant
-65,536) split over the ranks, timed the same way.  `roofline.kernel_ms` is the mean device-side span (first wave start
+(weak scaling: --num-envs per GPU; the only collective is the obs/rew/reset gather to rank 0, timed).  With --full
+the same line carries `strong_scaling`: BASELINE.json's fixed-total configs (MA-Ant 65,536 envs, ShadowHand 32,768,
+and Ant 65,536) split over the ranks, timed the same way.  `roofline.kernel_ms` is the mean device-side span (first wave start
 to last wave end, GPU wall clock) of the timed launches themselves.  Rank 0 prints ONE JSON line.  See DESIGN.md §7 for the roofline accounting.
 """
 import argparse
@@ -220,10 +225,48 @@ STRONG_CONFIGS = (("MAAnt", 65536, "BASELINE configs[3]: multi-agent Ant (4 agen
                   ("Ant", 65536, "Ant, 65,536 envs total (strong-scaling counterpart of the headline)"))
 
 
-def run_workload(task, n, object_type, args, world, rank, dev, gather_mode, seed, what=None, total=None):
+DUMP_BUDGET = 64 * 10**6   # bytes --dump-outputs may write in all (64 MB)
+
+
+def dump_outputs(out_dir, ret, rank):
+    """--dump-outputs: what the last timed VecTask.step returned (obs dict, rew, reset, the tensors in extras), as
+    out_dir/<name>.npy: float32, or float64 for integer and 64-bit tensors.  Above DUMP_BUDGET in all, the per-row
+    arrays keep one fixed seeded sample of rows (the same rows in each; their indices go to sample_rows.npy).
+    Ranks above 0 write <name>_rank<r>.npy.  Returns {name: shape} of what was written."""
+    import re
+    import numpy as np
+    import torch
+    obs, rew, reset, extras = ret
+    tensors = dict(obs)
+    tensors.update(rew=rew, reset=reset)
+    tensors.update({f"extras_{k}": v for k, v in extras.items() if isinstance(v, torch.Tensor)})
+    arrs = {}
+    for k, t in tensors.items():
+        t = t.detach().cpu()
+        f32 = t.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.bool, torch.uint8, torch.int8)
+        arrs[re.sub(r"[^0-9A-Za-z_]", "_", str(k))] = t.to(torch.float32 if f32 else torch.float64).numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    rows = rew.shape[0]
+    if total > DUMP_BUDGET:
+        keep = max(1, int(rows * 0.95 * DUMP_BUDGET / total))
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrs = {k: (a[idx] if a.ndim and a.shape[0] == rows else a) for k, a in arrs.items()}
+        arrs["sample_rows"] = idx.astype(np.float64)
+        total = sum(a.nbytes for a in arrs.values())
+        if total > DUMP_BUDGET:
+            raise RuntimeError(f"--dump-outputs: {total} bytes left after sampling rows, above {DUMP_BUDGET}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + (f"_rank{rank}" if rank else "") + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrs.items()}
+
+
+def run_workload(task, n, object_type, args, world, rank, dev, gather_mode, seed, what=None, total=None,
+                 dump_dir=None):
     """One workload: make() `n` envs on this rank, W warm-up steps, K timed steps between barrier + synchronize
-    (max over ranks), then a separate kernel-duration pass (HIP events around each of --kernel-samples launches on
-    the launch stream, median; the timed region has no events, so its wall time is not diluted by them)."""
+    (max over ranks), the last timed step's outputs to `dump_dir` if given, and with --full a separate
+    kernel-duration pass (HIP events around each of --kernel-samples launches on the launch stream, median; the
+    timed region has no events, so its wall time is not diluted by them) and the steady-state sample."""
     import torch
     import torch.distributed as dist
     import migym
@@ -260,8 +303,9 @@ def run_workload(task, n, object_type, args, world, rank, dev, gather_mode, seed
     nspan = min(args.steps, 1024)
     env.kernel_span_begin(nspan)
     t0 = time.perf_counter()
+    ret = None
     for i in range(args.steps):
-        env.step(pool[i % 8])
+        ret = env.step(pool[i % 8])
     if gather is not None:
         gather.drain()   # the last step's rows have reached the root
     torch.cuda.synchronize()
@@ -271,24 +315,28 @@ def run_workload(task, n, object_type, args, world, rank, dev, gather_mode, seed
     spans = [float(x) for x in env.kernel_span_read(nspan) if x > 0]
     env.kernel_span_begin(0)
     span_ok = len(spans) == nspan
-    # HIP events around each of --kernel-samples further launches (untimed), for comparison: kernel + the event
-    # packets' dispatch latency; kernel_ms falls back to their median for a library built without the span hooks
+    # the returned tensors are the env's own buffers: copy them out before any further step overwrites them
+    dumped = dump_outputs(dump_dir, ret, rank) if (dump_dir and ret is not None) else None
+    # --full: HIP events around each of --kernel-samples further launches (untimed), for comparison: kernel + the
+    # event packets' dispatch latency; kernel_ms falls back to their median for a library built without the span hooks
     ks = max(1, args.kernel_samples)
-    starts = [torch.cuda.Event(enable_timing=True) for _ in range(ks)]
-    ends = [torch.cuda.Event(enable_timing=True) for _ in range(ks)]
-    for i in range(ks):
-        env.launch_events = (starts[i], ends[i])
-        env.step(pool[i % 8])
-    env.launch_events = None
-    if gather is not None:
-        gather.drain()
-    torch.cuda.synchronize()
-    ev = sorted(starts[i].elapsed_time(ends[i]) for i in range(ks))
-    event_ms = ev[ks // 2] if ks % 2 else 0.5 * (ev[ks // 2 - 1] + ev[ks // 2])
-    # steady state: a further untimed sample of the same rollout (a short timed run right after the first
+    event_ms = None
+    if args.full:
+        starts = [torch.cuda.Event(enable_timing=True) for _ in range(ks)]
+        ends = [torch.cuda.Event(enable_timing=True) for _ in range(ks)]
+        for i in range(ks):
+            env.launch_events = (starts[i], ends[i])
+            env.step(pool[i % 8])
+        env.launch_events = None
+        if gather is not None:
+            gather.drain()
+        torch.cuda.synchronize()
+        ev = sorted(starts[i].elapsed_time(ends[i]) for i in range(ks))
+        event_ms = ev[ks // 2] if ks % 2 else 0.5 * (ev[ks // 2 - 1] + ev[ks // 2])
+    # --full, steady state: a further untimed sample of the same rollout (a short timed run right after the first
     # reset is not steady state -- early-episode rows make the locomotion steps heavier, the hand's lighter)
     steady_ms = None
-    if args.steady_steps > 0:
+    if args.full and args.steady_steps > 0:
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -302,14 +350,16 @@ def run_workload(task, n, object_type, args, world, rank, dev, gather_mode, seed
             dist.barrier()
         steady_ms = 1e3 * (time.perf_counter() - t1) / args.steady_steps
     if not span_ok:
-        print(f"bench.py: the span hooks recorded {len(spans)} of {nspan} launches; kernel_ms from HIP events",
-              file=sys.stderr)
-    kern_ms = sum(spans) / len(spans) if span_ok else event_ms
+        print(f"bench.py: the span hooks recorded {len(spans)} of {nspan} launches; kernel_ms from HIP events"
+              + ("" if args.full else " needs --full"), file=sys.stderr)
+    kern_ms = sum(spans) / len(spans) if span_ok else event_ms   # None: no span hooks and no event pass
     if world > 1:
-        t = torch.tensor([elapsed, kern_ms, event_ms, steady_ms or 0.0], dtype=torch.float64,
+        t = torch.tensor([elapsed, kern_ms or 0.0, event_ms or 0.0, steady_ms or 0.0], dtype=torch.float64,
                          device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, kern_ms, event_ms = float(t[0]), float(t[1]), float(t[2])
+        elapsed = float(t[0])
+        kern_ms = float(t[1]) if kern_ms is not None else None
+        event_ms = float(t[2]) if event_ms is not None else None
         steady_ms = float(t[3]) if steady_ms is not None else None
     info = {"substeps": env.sim_params.substeps, "pos_iters": env.sim_params.pos_iters, "agents": env.num_agents,
             "solver": "TGS" if env.sim_params.solver_type == 1 else "PGS",
@@ -326,8 +376,9 @@ def run_workload(task, n, object_type, args, world, rank, dev, gather_mode, seed
     r = {"value": value, "unit": "env-steps/s", "ms_per_step": 1e3 * elapsed / args.steps, "kernel_ms": kern_ms,
          "kernel_ms_sample": (f"mean over the {nspan} timed launches of each launch's device-side span (first wave "
                               f"start to last wave end, GPU wall clock; max over ranks)") if span_ok else
-                             f"median of HIP events around {ks} launches (no span hooks in this library)",
-         "event_ms": event_ms,
+                             (f"median of HIP events around {ks} launches (no span hooks in this library)"
+                              if event_ms is not None else None),
+         "event_ms": event_ms, "dumped": dumped,
          "steady_state_ms": steady_ms,
          "steady_state_value": (n * world / (steady_ms * 1e-3)) if steady_ms else None,
          "steady_state_sample": (f"{args.steady_steps} further steps of the same rollout after the timed ones and the "
@@ -349,7 +400,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--task", default="Ant")
     ap.add_argument("--num-envs", type=int, default=65536, help="envs per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, everything that takes runs of its own: the HIP-event pass (event_ms), "
+                         "the steady-state sample, strong_scaling, cpu_baseline and baseline_config0 (each with its "
+                         "own switch below); off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (obs, rew, reset, extras) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB in all (a fixed seeded sample of rows above that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline / baseline_config0")
     ap.add_argument("--gather", default=None, choices=["all", "root", "none"],
                     help="concatenate obs/rew/reset of every rank each step, inside the timed region "
                          "(migym.dist.PackedGather: rows packed by the kernel, double-buffered, overlapped with "
@@ -371,6 +429,8 @@ def main():
     ap.add_argument("--object-type", default="block", choices=["block", "egg", "pen"],
                     help="ShadowHand objectType (shadow_hand.py:86-100)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (it is the number of timed steps)")
 
     import torch
     import torch.distributed as dist
@@ -390,11 +450,12 @@ def main():
     import migym
     n = args.num_envs
     gather_mode = args.gather or ("root" if world > 1 else "none")
-    head = run_workload(args.task, n, args.object_type, args, world, rank, dev, gather_mode, seed=rank)
-    # strong scaling: BASELINE.json's fixed-total multi-GPU configs, each rank stepping total / world envs of one
-    # node-size rollout (global env ids rank * n_rank ..., so the shards are slices of it), same timing rules
+    head = run_workload(args.task, n, args.object_type, args, world, rank, dev, gather_mode, seed=rank,
+                        dump_dir=args.dump_outputs)
+    # --full, strong scaling: BASELINE.json's fixed-total multi-GPU configs, each rank stepping total / world envs of
+    # one node-size rollout (global env ids rank * n_rank ..., so the shards are slices of it), same timing rules
     strong = []
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         for task, total, what in STRONG_CONFIGS:
             if total % world:
                 continue
@@ -402,15 +463,15 @@ def main():
                                        what=what, total=total))
     value = head["value"]
     ms_per_step, kern_ms = head["ms_per_step"], head["kernel_ms"]
-    if kern_ms > ms_per_step and rank == 0:   # the device span cannot exceed the steady-state time per step
+    if kern_ms is not None and kern_ms > ms_per_step and rank == 0:   # the device span cannot exceed the time per step
         print(f"bench.py: kernel_ms {kern_ms:.4f} > ms_per_step {ms_per_step:.4f}", file=sys.stderr)
     if rank == 0:
         per_launch = ALGO_BYTES[args.task] * n
-        achieved = per_launch / (kern_ms * 1e-3)
         env = head["env_info"]
         out = {
             "metric": "env-steps/sec (whole node) at num_envs=65536; 1/2/4/8 MI355X scaling",
             "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "steady_state_ms": head["steady_state_ms"], "steady_state_value": head["steady_state_value"],
             "steady_state_sample": head["steady_state_sample"],
@@ -425,28 +486,35 @@ def main():
                                      if head["gathered"] else None,
                        "parallelism": f"env-sharded x{world}", "team_layout": env.get("team_layout"),
                        **({"object_type": args.object_type} if args.task == "ShadowHand" else {})},
-            "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK, **pmc_traffic(args.task, n, kern_ms, args.object_type),
-                         "kernel": "k_hand_step" if args.task == "ShadowHand" else "k_env_step",
-                         "kernel_ms": kern_ms, "kernel_ms_sample": head["kernel_ms_sample"],
-                         "kernel_ms_scope": ("the fused step kernel only: with work ordering on (DESIGN.md §3) the "
-                                             "sort's two small launches before it (k_ohist, k_oscatter; rocprof "
-                                             "profiles/r06/*kernel_stats.csv) lie outside kernel_ms and inside "
-                                             "event_ms and ms_per_step"),
-                         "kernel_ms_le_ms_per_step": kern_ms <= ms_per_step,
-                         "event_ms": head["event_ms"],
-                         "event_ms_note": "HIP events around each launch of the same pass: kernel + the event "
-                                          "packets' dispatch latency, so above kernel_ms",
-                         "algo_bytes_per_env_step": ALGO_BYTES[args.task]},
+            "roofline": None,   # a plain run of a library without the span hooks: kernel_ms needs --full
         }
+        if kern_ms is not None:   # from the timed launches' own spans (or, with --full, the event pass): no extra run
+            achieved = per_launch / (kern_ms * 1e-3)
+            out["roofline"] = {
+                "bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK, **pmc_traffic(args.task, n, kern_ms, args.object_type),
+                "kernel": "k_hand_step" if args.task == "ShadowHand" else "k_env_step",
+                "kernel_ms": kern_ms, "kernel_ms_sample": head["kernel_ms_sample"],
+                "kernel_ms_scope": ("the fused step kernel only: with work ordering on (DESIGN.md §3) the "
+                                    "sort's two small launches before it (k_ohist, k_oscatter; rocprof "
+                                    "profiles/r06/*kernel_stats.csv) lie outside kernel_ms and inside "
+                                    "event_ms and ms_per_step"),
+                "kernel_ms_le_ms_per_step": kern_ms <= ms_per_step,
+                "event_ms": head["event_ms"],
+                "event_ms_note": ("HIP events around each launch of the same pass: kernel + the event "
+                                  "packets' dispatch latency, so above kernel_ms") if args.full else
+                                 "measured with --full only",
+                "algo_bytes_per_env_step": ALGO_BYTES[args.task]}
+        if head["dumped"] is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": head["dumped"]}
         if strong:
-            out["strong_scaling"] = [{k: v for k, v in r.items() if k != "env_info"} for r in strong]
-        if not args.no_cpu_baseline and world == 1:
+            out["strong_scaling"] = [{k: v for k, v in r.items() if k not in ("env_info", "dumped")} for r in strong]
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.task, args.cpu_seconds, n, args.object_type, args.solver)
             except Exception as ex:  # noqa: BLE001
                 out["cpu_baseline"] = {"error": repr(ex)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["baseline_config0"] = baseline_config0(dev)
             except Exception as ex:  # noqa: BLE001

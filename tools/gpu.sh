@@ -35,7 +35,7 @@ bench_one() {  # $1 = out file, $2 = SPEC, rest = extra bench args
   local out=$1 spec=$2; shift 2
   IFS=: read -r t n o k <<< "$spec"; o=${o:-block}; k=${k:-200}
   timeout -k 10 400 python bench.py --task "$t" --num-envs "$n" --object-type "$o" --steps "$k" --warmup 20 \
-    "$@" > "$out" 2> "${out%.json}.err"
+    --full "$@" > "$out" 2> "${out%.json}.err"
   local rc=$?
   if [ $rc -ne 0 ]; then echo "bench $spec rc=$rc"; tail -5 "${out%.json}.err"; exit $rc; fi
 }
@@ -59,7 +59,7 @@ pmc_passes() {  # $1 dir, $2 task, $3 n, $4 obj
     [ "${PMC_PASSES:-4}" -lt $i ] && break
     echo "== pmc pass $i ($2 $3 $4): $C"
     timeout -k 10 300 rocprofv3 --pmc $C -d "$1" -o pass$i --output-format csv -- python bench.py --task "$2" \
-      --num-envs "$3" --object-type "$4" --steps 20 --warmup 3 --no-cpu-baseline --no-strong > "$1/pass$i.log" 2>&1
+      --num-envs "$3" --object-type "$4" --steps 20 --warmup 3 --full --no-cpu-baseline --no-strong > "$1/pass$i.log" 2>&1
     local rc=$?; echo "rc=$rc"
     [ $rc -eq 0 ] || { tail -3 "$1/pass$i.log"; exit $rc; }
   done
@@ -130,14 +130,14 @@ case $mode in
     for gm in all root; do
       echo "== torchrun x$N gather=$gm"
       timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 \
-        --master-port $((29500 + RANDOM % 1000)) bench.py --gpus "$N" --steps 20 --warmup 5 --backend gloo --steady-steps 0 \
+        --master-port $((29500 + RANDOM % 1000)) bench.py --gpus "$N" --steps 20 --warmup 5 --full --backend gloo --steady-steps 0 \
         --gather $gm > gpurun_out/multirank/x${N}_$gm.log 2>&1
       rc=$?; echo "rc=$rc"; tail -n 2 gpurun_out/multirank/x${N}_$gm.log
       [ $rc -eq 0 ] || exit $rc
     done ;;
   profile)   # a round's kernel stats + PMC passes per kernel instance (copy the pmc_*.json into profiles/R after)
     R=${1:?round}; OUT=gpurun_out/$R; mkdir -p "$OUT"
-    "$0" stats "$R/stats" --steps 50 --warmup 5 --no-cpu-baseline --no-strong || exit 1
+    "$0" stats "$R/stats" --steps 50 --warmup 5 --full --no-cpu-baseline --no-strong || exit 1
     for spec in "Ant 65536 block" "Humanoid 32768 block" "ShadowHand 16384 block" "ShadowHand 16384 egg" \
                 "ShadowHand 16384 pen" "MAAnt 8192 block" "ShadowHand 4096 block"; do
       set -- $spec
