@@ -53,6 +53,8 @@
 extern "C" {
 #endif
 
+/* stays 7 with the dynamics-tensor entry points (mg_dynamics_*, mg_osc_torques): they only add symbols, no existing
+ * struct or call changes, and tests/test_abi.py pins mg_version() == 7 */
 #define MG_VERSION 7
 
 #define MG_MAX_NODES 40
@@ -515,6 +517,53 @@ typedef struct mg_replay {
 } mg_replay;
 int mg_env_step_replay(mg_sim* sim, const mg_task_params* tp, const mg_task_buffers* tb, const mg_replay* rp,
                        void* stream);
+
+/* ---- dynamics tensors and operational-space control (fixed-base articulations) ----
+ * gym.acquire_jacobian_tensor / acquire_mass_matrix_tensor (+ refresh_*): franka_reach_MA.py:564-565, 891-911.
+ * Fixed-base models only: all three calls return MG_EINVAL for a free-base model (gym's floating-base tensors
+ * carry six base columns whose convention is a separate decision, out of scope here), and for a model with a free
+ * object (hand tasks: three root rows per env).  DOF j is node j + 1;
+ * PhysX parity of the values is not pinned: the kernels are held to the fp64 oracle. */
+typedef struct mg_dynamics_views {
+  float* jacobian;     /* (N*A, nB-1, 6, nD): row b-1 = body b (the fixed base link has no row, as gym);
+                          [linear(3); angular(3)] of the body ORIGIN, world frame; or NULL */
+  float* mass_matrix;  /* (N*A, nD, nD): joint-space inertia H(q) + diag(armature); no implicit damping or
+                          stiffness terms; symmetric, both triangles written; or NULL */
+} mg_dynamics_views;
+int mg_dynamics_bind(mg_sim* sim, const mg_dynamics_views* views);
+/* one launch: both bound tensors from the bound root_states / dof_state (and env_props, when bound: the masses
+ * and armatures of the actor that is simulated) */
+int mg_dynamics_refresh(mg_sim* sim, void* stream);
+
+/* FrankaReachMA._compute_osc_torques (franka_reach_MA.py:770-802) as one launch, per actor:
+ *   A = J M^-1 J^T (6 x 6), u = J^T A^-1 (kp * dpose - kd * eef_vel),
+ *   u_null = kd_null * (-qd) + kp_null * wrap(default_dof_pos - q), wrap(x) = ((x + pi) mod 2 pi) - pi (floor-mod),
+ *   u += (I - J^T A^-1 J M^-1) M u_null, evaluated as M u_null - J^T A^-1 J u_null (equal algebraically, no M^-1),
+ *   out = clamp(u, -effort_limit, effort_limit)
+ * with M the leading arm_dofs block of the full tree's mass matrix (the gripper's inertia included) and J the
+ * arm_dofs leading columns of body jac_body's Jacobian rows, both computed in the kernel from the bound state (no J
+ * or M goes through memory) unless jac_in / mm_in inject them.  M and A are factored by Cholesky; an actor whose
+ * factorisation fails (a non-positive pivot: a singular pose, a massless model) gets zeros, never NaN. */
+typedef struct mg_osc_args {
+  int32_t arm_dofs;          /* 1..7: the leading DOFs that are controlled */
+  int32_t jac_body;          /* body whose Jacobian rows are used (1 <= jac_body < nB) */
+  const float* dpose;        /* (n, 6) */
+  const float* eef_vel;      /* 6 floats per actor [linear; angular], eef_vel_stride floats apart: a contiguous
+                              * (n, 6) tensor (stride 6) or columns 7:13 of a body in rigid_body_states (stride 13 nB) */
+  int64_t eef_vel_stride;
+  float kp[6], kd[6];
+  float kp_null[7], kd_null[7];
+  float default_dof_pos[7];
+  float effort_limit[7];     /* +inf = no clamp */
+  float* out;                /* the first out_cols torques of actor a at out + a * out_stride */
+  int64_t out_stride;        /* out = dof_actuation, out_stride = nD fuses the write into the actuation tensor */
+  int32_t out_cols;          /* 1..arm_dofs (the reference writes columns :6, franka_reach_MA.py:817) */
+  int32_t pad_osc;
+  const float* jac_in;       /* (n, 6, arm_dofs) or NULL: both given or both NULL */
+  const float* mm_in;        /* (n, arm_dofs, arm_dofs) or NULL */
+} mg_osc_args;
+int mg_osc_torques(mg_sim* sim, const mg_osc_args* args, void* stream);
+size_t mg_osc_args_sizeof(void);
 
 /* Measurement aid (no reference counterpart; bench.py's roofline.kernel_ms): the device-side duration of the
  * fused step kernel, from the first wave's start to the last wave's end on the GPU's constant wall clock

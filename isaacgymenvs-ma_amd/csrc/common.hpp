@@ -55,6 +55,10 @@ struct mg_sim {
   unsigned long long* d_span;
   int span_cap, span_next, span_stride;
   int span_waves[1024];  // waves of each recorded launch
+  // dynamics tensors (dynamics_tensors.hpp): the model as those kernels read it (fixed-base models; nullptr
+  // otherwise) and the tensors mg_dynamics_bind bound
+  void* d_dyn;
+  mg_dynamics_views dyn;
 };
 
 // the step kernels' ordering arguments: the bucket lists this launch reads (rcnt nullptr: slot = env) and writes

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "dispatch.hpp"
+#include "dynamics_tensors.hpp"
 #include "hand_task.hpp"
 #include "task.hpp"
 
@@ -677,6 +678,21 @@ int mg_sim_create(const mg_model* model, const mg_sim_params* params, int32_t nu
     mg_sim_destroy(s);
     return fail(MG_ENOMEM, "mg_sim_create: hipMalloc(work queue) failed");
   }
+  // the dynamics-tensor kernels' model (mg_dynamics_refresh, mg_osc_torques): fixed-base articulations only
+  s->d_dyn = nullptr;
+  s->dyn = mg_dynamics_views{nullptr, nullptr};
+  if (model->fixed_base && model->num_nodes >= 2) {
+    bool ok = true;
+    for (int b = 0; b < model->num_bodies; b++)
+      ok = ok && model->body_node[b] >= 0 && model->body_node[b] < model->num_nodes;
+    mgd::DynModel dm;
+    mgd::build_dyn_model(*model, &dm);
+    if (ok && (hipMalloc(&s->d_dyn, sizeof(dm)) != hipSuccess ||
+               hipMemcpy(s->d_dyn, &dm, sizeof(dm), hipMemcpyHostToDevice) != hipSuccess)) {
+      mg_sim_destroy(s);
+      return fail(MG_ENOMEM, "mg_sim_create: hipMalloc(dynamics model) failed");
+    }
+  }
   if (mgi::team_size(s->host_model, s->params.max_contacts) > 0) {
     const int rc = mgi::dispatch<mgi::BuildTile>(s->host_model, s->params.max_contacts, s->layout_n, s);
     if (rc) {
@@ -775,6 +791,7 @@ int mg_sim_destroy(mg_sim* sim) {
   if (sim->d_cost) (void)hipFree(sim->d_cost);
   if (sim->d_osort) (void)hipFree(sim->d_osort);
   if (sim->d_span) (void)hipFree(sim->d_span);
+  if (sim->d_dyn) (void)hipFree(sim->d_dyn);
   delete sim;
   return MG_OK;
 }
@@ -1162,6 +1179,85 @@ int mg_env_step_replay(mg_sim* sim, const mg_task_params* tp, const mg_task_buff
   if (sim && sim->host_model.obj_type && (!rp->root_states || !rp->rigid_body_states))
     return fail(MG_EINVAL, "mg_env_step_replay: hand tasks need root and rigid-body states");
   return env_step(sim, tp, tb, rp, stream);
+}
+
+// ---- dynamics tensors and the fused operational-space controller (dynamics_tensors.hpp)
+size_t mg_osc_args_sizeof(void) { return sizeof(mg_osc_args); }
+
+// the shared argument check: a bound, fixed-base sim
+static int dynamics_sim_ok(const mg_sim* sim, const char* who, bool need_bound) {
+  if (!sim) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
+  if (!sim->host_model.fixed_base)
+    return fail(MG_EINVAL, std::string(who) + ": dynamics tensors need a fixed-base model (the base columns of gym's "
+                                              "floating-base tensors are not implemented)");
+  // hand-task envs hold three root rows each (articulation, object, goal): the kernels index one row per actor
+  if (sim->host_model.obj_type)
+    return fail(MG_EINVAL, std::string(who) + ": models with a free object (hand tasks) are not supported");
+  if (!sim->d_dyn) return fail(MG_EINVAL, std::string(who) + ": the model has no DOFs or a body outside its nodes");
+  if (need_bound && !sim->bound) return fail(MG_EINVAL, std::string(who) + ": sim not bound");
+  return MG_OK;
+}
+
+int mg_dynamics_bind(mg_sim* sim, const mg_dynamics_views* views) {
+  if (int rc = dynamics_sim_ok(sim, "mg_dynamics_bind", false)) return rc;
+  if (!views) return fail(MG_EINVAL, "mg_dynamics_bind: bad arguments");
+  sim->dyn = *views;
+  return MG_OK;
+}
+
+int mg_dynamics_refresh(mg_sim* sim, void* stream) {
+  if (int rc = dynamics_sim_ok(sim, "mg_dynamics_refresh", true)) return rc;
+  if (!sim->dyn.jacobian && !sim->dyn.mass_matrix) return fail(MG_EINVAL, "mg_dynamics_refresh: no tensor bound");
+  const int blocks = (sim->n + mgd::kTeams - 1) / mgd::kTeams;
+  hipLaunchKernelGGL(mgd::k_dynamics_refresh, dim3(blocks), dim3(64), mgd::scratch_bytes(sim->host_model.num_nodes),
+                     (hipStream_t)stream, (const mgd::DynModel*)sim->d_dyn, sim->n, (const float*)sim->views.root_states,
+                     (const float*)sim->views.dof_state, sim->views.env_props, sim->views.env_props_stride,
+                     sim->dyn.jacobian, sim->dyn.mass_matrix);
+  return check_launch("mg_dynamics_refresh");
+}
+
+int mg_osc_torques(mg_sim* sim, const mg_osc_args* a, void* stream) {
+  if (int rc = dynamics_sim_ok(sim, "mg_osc_torques", true)) return rc;
+  const int nd = sim->host_model.num_nodes - 1;
+  if (!a || !a->dpose || !a->eef_vel || !a->out) return fail(MG_EINVAL, "mg_osc_torques: bad arguments");
+  if (a->arm_dofs < 1 || a->arm_dofs > mgd::kOscMax || a->arm_dofs > nd)
+    return fail(MG_EINVAL, "mg_osc_torques: arm_dofs must be 1..7 and at most the model's DOFs");
+  if (a->jac_body < 1 || a->jac_body >= sim->host_model.num_bodies)
+    return fail(MG_EINVAL, "mg_osc_torques: jac_body must name a body other than the base link");
+  if (a->out_cols < 1 || a->out_cols > a->arm_dofs || a->out_stride < a->out_cols || a->eef_vel_stride < 6)
+    return fail(MG_EINVAL, "mg_osc_torques: out_cols must be 1..arm_dofs, out_stride >= out_cols, eef_vel_stride >= 6");
+  if ((a->jac_in == nullptr) != (a->mm_in == nullptr))
+    return fail(MG_EINVAL, "mg_osc_torques: jac_in and mm_in are given together or not at all");
+  mgd::OscParams p;
+  p.arm_dofs = a->arm_dofs;
+  p.jac_body = a->jac_body;
+  p.out_cols = a->out_cols;
+  p.nd = nd;
+  p.dpose = a->dpose;
+  p.eef_vel = a->eef_vel;
+  p.eef_vel_stride = a->eef_vel_stride;
+  for (int k = 0; k < 6; k++) { p.kp[k] = a->kp[k]; p.kd[k] = a->kd[k]; }
+  for (int k = 0; k < mgd::kOscMax; k++) {
+    p.kp_null[k] = a->kp_null[k];
+    p.kd_null[k] = a->kd_null[k];
+    p.default_dof_pos[k] = a->default_dof_pos[k];
+    p.effort_limit[k] = a->effort_limit[k];
+  }
+  p.out = a->out;
+  p.out_stride = a->out_stride;
+  p.jac_in = a->jac_in;
+  p.mm_in = a->mm_in;
+  const mgd::DynModel* dm = (const mgd::DynModel*)sim->d_dyn;
+  const float* root = sim->views.root_states;
+  const float* dof = sim->views.dof_state;
+  if (a->jac_in)
+    hipLaunchKernelGGL(mgd::k_osc<true>, dim3((sim->n + 63) / 64), dim3(64), 0, (hipStream_t)stream, dm, sim->n, p, root,
+                       dof, sim->views.env_props, sim->views.env_props_stride);
+  else
+    hipLaunchKernelGGL(mgd::k_osc<false>, dim3((sim->n + mgd::kTeams - 1) / mgd::kTeams), dim3(64),
+                       mgd::scratch_bytes(sim->host_model.num_nodes), (hipStream_t)stream, dm, sim->n, p, root, dof,
+                       sim->views.env_props, sim->views.env_props_stride);
+  return check_launch("mg_osc_torques");
 }
 
 

@@ -127,6 +127,20 @@ class Replay(C.Structure):
                 ("pre_dof_state", C.c_void_p)]
 
 
+class DynamicsViews(C.Structure):
+    """mg_dynamics_views: the Jacobian (N*A, nB-1, 6, nD) and mass-matrix (N*A, nD, nD) tensors."""
+    _fields_ = [("jacobian", C.c_void_p), ("mass_matrix", C.c_void_p)]
+
+
+class OscArgs(C.Structure):
+    """mg_osc_args: one operational-space control launch (franka_reach_MA.py:770-802)."""
+    _fields_ = [("arm_dofs", C.c_int32), ("jac_body", C.c_int32), ("dpose", C.c_void_p), ("eef_vel", C.c_void_p),
+                ("eef_vel_stride", C.c_int64), ("kp", C.c_float * 6), ("kd", C.c_float * 6),
+                ("kp_null", C.c_float * 7), ("kd_null", C.c_float * 7), ("default_dof_pos", C.c_float * 7),
+                ("effort_limit", C.c_float * 7), ("out", C.c_void_p), ("out_stride", C.c_int64),
+                ("out_cols", C.c_int32), ("pad_osc", C.c_int32), ("jac_in", C.c_void_p), ("mm_in", C.c_void_p)]
+
+
 def model_bytes(spec) -> np.ndarray:
     """mg_model POD for a ModelSpec (numpy structured scalar; pass .ctypes.data)."""
     return np.ascontiguousarray(_model.pack_model(spec))
@@ -183,6 +197,10 @@ EXPORTS = {
     "mg_dr_apply": (C.c_int, [C.POINTER(DrApplyArgs), C.c_void_p]),
     "mg_dr_noise": (C.c_int, [C.POINTER(DrNoiseArgs), C.c_void_p]),
     "mg_sim_set_params": (C.c_int, [C.c_void_p, C.POINTER(SimParams)]),
+    "mg_dynamics_bind": (C.c_int, [C.c_void_p, C.POINTER(DynamicsViews)]),
+    "mg_dynamics_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mg_osc_torques": (C.c_int, [C.c_void_p, C.POINTER(OscArgs), C.c_void_p]),
+    "mg_osc_args_sizeof": (C.c_size_t, []),
 }
 
 _LIB = None
@@ -204,7 +222,8 @@ def check_layout(lib):
     sizes = {"mg_model_sizeof": _model.MODEL_DTYPE.itemsize, "mg_task_params_sizeof": C.sizeof(TaskParams),
              "mg_task_buffers_sizeof": C.sizeof(TaskBuffers), "mg_sim_params_sizeof": C.sizeof(SimParams),
              "mg_state_views_sizeof": C.sizeof(StateViews), "mg_dr_desc_sizeof": C.sizeof(DrDesc),
-             "mg_dr_apply_args_sizeof": C.sizeof(DrApplyArgs), "mg_dr_noise_args_sizeof": C.sizeof(DrNoiseArgs)}
+             "mg_dr_apply_args_sizeof": C.sizeof(DrApplyArgs), "mg_dr_noise_args_sizeof": C.sizeof(DrNoiseArgs),
+             "mg_osc_args_sizeof": C.sizeof(OscArgs)}
     for fn, py in sizes.items():
         c = getattr(lib, fn)()
         if c != py:

@@ -943,6 +943,11 @@ def load_builtin(name) -> ModelSpec:
     return ModelSpec.from_json(os.path.join(ASSET_DIR, name + ".json"))
 
 
+def load_json(path) -> ModelSpec:
+    """Load a model table by path (the format of the shipped tables; e.g. a test fixture under tests/golden/)."""
+    return ModelSpec.from_json(path)
+
+
 def hand_object(kind: str) -> Dict:
     """The free object of ShadowHand's objectType (shadow_hand.py:86-100): block = cube_multicolor.urdf,
     egg = open_ai_assets/hand/egg.xml (ellipsoid), pen = open_ai_assets/hand/pen.xml (capsule).  Shipped

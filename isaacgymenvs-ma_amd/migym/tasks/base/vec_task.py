@@ -109,6 +109,10 @@ class VecTask(DomainRandomizationMixin, Env):
     # whether the reference task calls gym.acquire_dof_force_tensor (humanoid.py:85-86, shadow_hand.py:157-159): the
     # DOF-force view is bound, and the fused step computes the forces, only then
     acquires_dof_force = False
+    # dynamics tensors (acquire_jacobian_tensor / acquire_mass_matrix_tensor): created on first use; _dyn_covered
+    # names the tensor whose refresh call the last launch already served
+    _dyn = None
+    _dyn_covered = None
 
     def __init__(self, config, rl_device, sim_device, graphics_device_id, headless, virtual_screen_capture=False,
                  force_render=False):
@@ -242,6 +246,7 @@ class VecTask(DomainRandomizationMixin, Env):
                 self._dr_step(self.reset_buf, pending_increment=self.control_steps > 0)
             else:
                 self._dr["mask"].copy_(self.reset_buf)   # the resets post_physics_step will apply
+        self._dyn_covered = None   # the state moves: the next dynamics-tensor refresh launches again
         self._actions_in = a   # keep alive until the launch has consumed it
         tb = self._tb
         tb.actions = a.data_ptr()
@@ -303,6 +308,53 @@ class VecTask(DomainRandomizationMixin, Env):
         """gym.refresh_net_contact_force_tensor (franka_reach_MA.py:563): a no-op -- the bound tensor is written by
         the step itself"""
 
+    def _dynamics(self):
+        """the task's DynamicsTensors (migym/dynamics.py); free-base tasks raise NotImplementedError with the
+        library's message (mg_dynamics_bind)"""
+        d = getattr(self, "_dyn", None)
+        if d is None:
+            from migym.dynamics import DynamicsTensors
+            d = self._dyn = DynamicsTensors(self._lib, self.sim, self.model_spec, self.num_actors, self.device)
+        return d
+
+    def acquire_jacobian_tensor(self) -> torch.Tensor:
+        """gym.acquire_jacobian_tensor + gymtorch.wrap_tensor (franka_reach_MA.py:894-895) for every actor at once:
+        (N*A, nB-1, 6, nD), row b-1 = body b's origin, [linear; angular], world frame (the fixed base link has no
+        row).  Filled by refresh_jacobian_tensors."""
+        self._dyn_covered = None   # a tensor bound after a launch was not written by it
+        return self._dynamics().acquire_jacobian()
+
+    def acquire_mass_matrix_tensor(self) -> torch.Tensor:
+        """gym.acquire_mass_matrix_tensor + gymtorch.wrap_tensor (franka_reach_MA.py:906-907): (N*A, nD, nD), the
+        joint-space inertia + diag(armature).  Filled by refresh_mass_matrix_tensors."""
+        self._dyn_covered = None
+        return self._dynamics().acquire_mass_matrix()
+
+    def _refresh_dynamics(self, which):
+        # one launch writes every acquired tensor: the call for the other tensor that directly follows is covered by
+        # it (step / reset / set_env_state end the pairing; a caller that writes the state tensors itself between the
+        # two calls refreshes again)
+        d = self._dynamics()
+        if self._dyn_covered == which:
+            self._dyn_covered = None
+            return
+        d.refresh()
+        self._dyn_covered = "mass_matrix" if which == "jacobian" else "jacobian"
+
+    def refresh_jacobian_tensors(self):
+        """gym.refresh_jacobian_tensors (franka_reach_MA.py:564, 899)"""
+        self._refresh_dynamics("jacobian")
+
+    def refresh_mass_matrix_tensors(self):
+        """gym.refresh_mass_matrix_tensors (franka_reach_MA.py:565, 909)"""
+        self._refresh_dynamics("mass_matrix")
+
+    def compute_osc_torques(self, dpose, eef_vel, *, jac_body, **kw) -> torch.Tensor:
+        """FrankaReachMA._compute_osc_torques (franka_reach_MA.py:770-802) as one fused launch from the current
+        state, with no Jacobian or mass matrix in memory; arguments as DynamicsTensors.osc_torques
+        (``out=self.dof_actuation, out_stride=self.num_dof`` writes the torques into the actuation tensor)."""
+        return self._dynamics().osc_torques(dpose, eef_vel, jac_body=jac_body, **kw)
+
     def kernel_span_begin(self, n: int):
         """record the device-side duration (first wave start -> last wave end, GPU wall clock) of the next n fused
         step launches (mg_kernel_span_begin; 0 stops recording).  A measurement aid: bench.py's kernel_ms"""
@@ -363,6 +415,7 @@ class VecTask(DomainRandomizationMixin, Env):
         a reference checkpoint holds) is a no-op."""
         if env_state is None:
             return
+        self._dyn_covered = None
         for k, v in env_state.items():
             cur = getattr(self, k, None)
             if isinstance(cur, torch.Tensor):
@@ -409,6 +462,7 @@ class VecTask(DomainRandomizationMixin, Env):
         ids = torch.as_tensor(env_ids, device=self.device).flatten().to(torch.int64)
         if ids.numel() == 0:
             return
+        self._dyn_covered = None
         if self.num_agents > 1:
             A, N = self.num_agents, self.num_envs
             full = torch.bincount(ids // A, minlength=N)[:N] >= A

@@ -23,6 +23,12 @@ them from migym/assets/*.json.
             (ellipsoid), pen = mjcf/open_ai_assets/hand/pen.xml (capsule along the body z); mass and
             principal inertia from the geom at MJCF's default density 1000; the object body's own
             MJCF pose is replaced by the actor pose (as the cube's URDF origin is).
+  Franka    assets/urdf/franka_description/robots/franka_panda_gripper.urdf (franka_reach_MA.py:254-262:
+            fix_base_link, collapse_fixed_joints False, disable_gravity).  A TEST FIXTURE, written to
+            tests/golden/franka_panda.json and not shipped under migym/assets: the URDF has no <inertial>, and
+            Isaac Gym derives the masses from the collision meshes at its default density; the fixture takes
+            each link's mass, COM and inertia from the convex hull of its collision mesh at 1000 kg/m^3
+            (hull_mass_properties), which stands in for whatever PhysX cooks.
 """
 import json
 import os
@@ -78,6 +84,85 @@ def reduced_hull(v, max_verts=160, tol=1e-5):
         if not any(np.allclose(q, p2, atol=1e-7) for p2 in planes):
             planes.append(q)
     return v[sel], planes, float(max(out.max(), 0.0))
+
+
+def hull_mass_properties(verts, density):
+    """(mass, COM, inertia about the COM) of the convex hull of `verts` at uniform `density`, by signed-tetrahedron
+    integration: every hull triangle (a, b, c), wound outward, spans a tetrahedron with a point inside the hull;
+    its volume is det[a b c] / 6, its centroid (a + b + c) / 4, and its second moment about that point
+    V / 20 (s s^T + a a^T + b b^T + c c^T) with s = a + b + c."""
+    from scipy.spatial import ConvexHull
+    v = np.asarray(verts, dtype=np.float64)
+    ref = v.mean(0)
+    h = ConvexHull(v)
+    vol, mom, C = 0.0, np.zeros(3), np.zeros((3, 3))
+    for tri, eq in zip(h.simplices, h.equations):
+        a, b, c = (v[i] - ref for i in tri)
+        if np.dot(np.cross(b - a, c - a), eq[:3]) < 0:   # wind the triangle along the outward normal
+            b, c = c, b
+        V = np.dot(a, np.cross(b, c)) / 6.0
+        s = a + b + c
+        vol += V
+        mom += V * s / 4.0
+        C += V / 20.0 * (np.outer(s, s) + np.outer(a, a) + np.outer(b, b) + np.outer(c, c))
+    com = mom / vol
+    I0 = np.trace(C) * np.eye(3) - C                   # about ref
+    Ic = I0 - vol * (np.dot(com, com) * np.eye(3) - np.outer(com, com))
+    return density * vol, ref + com, density * Ic
+
+
+def obj_vertices(path):
+    """vertices of a Wavefront OBJ mesh (the `v x y z` lines), mesh frame."""
+    v = [[float(x) for x in ln.split()[1:4]] for ln in open(path) if ln.startswith("v ")]
+    return np.unique(np.array(v, dtype=np.float64), axis=0)
+
+
+FRANKA_URDF = "assets/urdf/franka_description/robots/franka_panda_gripper.urdf"
+FRANKA_DENSITY = 1000.0   # gymapi.AssetOptions.density default
+FRANKA_JSON = os.path.join(HERE, "..", "tests", "golden", "franka_panda.json")
+
+
+def franka_panda():
+    """The Panda arm + gripper as a model table with hull-density masses (see the module docstring).  Mesh
+    collision geoms are not imported (load_urdf skips them); the URDF effort limits are kept per DOF node."""
+    path = os.path.join(REF, FRANKA_URDF)
+    spec = M.load_urdf(path, "franka_panda", fix_base=True)
+    root = ET.parse(path).getroot()
+    pkg = os.path.join(REF, "assets/urdf")
+    accs, masses = {}, {}
+    for link in root.findall("link"):
+        bi = spec.body_index(link.get("name"))
+        body = spec.bodies[bi]
+        T = M.Xform(np.array(body.pos), np.array(body.quat))       # body frame in its node
+        bacc = M._MassAccum()
+        for col in link.findall("collision"):
+            mesh = col.find("geometry").find("mesh")
+            if mesh is None:
+                continue
+            o = col.find("origin")
+            Xc = M.Xform() if o is None else M.Xform(np.array(M._floats(o.get("xyz", "0 0 0"))),
+                                                     M.quat_from_rpy(*M._floats(o.get("rpy", "0 0 0"))))
+            m, c, I = hull_mass_properties(obj_vertices(mesh.get("filename").replace("package:/", pkg)),
+                                           FRANKA_DENSITY)
+            Xn = T.compose(Xc)
+            R = M.qmat(Xn.rot)
+            accs.setdefault(body.node, M._MassAccum()).add(m, Xn.apply(c), R @ I @ R.T)
+            Rb = M.qmat(Xc.rot)
+            bacc.add(m, Xc.apply(c), Rb @ I @ Rb.T)
+        m, c, _ = bacc.result()
+        body.mass, body.com = float(m), [float(x) for x in c]
+        masses[body.name] = body.mass
+    for i, acc in accs.items():
+        m, c, Ic = acc.result()
+        n = spec.nodes[i]
+        n.mass, n.com, n.inertia = float(m), [float(x) for x in c], M._inertia6(Ic)
+    for j in root.findall("joint"):
+        if j.get("name") in spec.dof_names and j.find("limit") is not None:
+            spec.nodes[1 + spec.dof_index(j.get("name"))].effort_limit = float(j.find("limit").get("effort", "0"))
+    spec.geoms = [g for g in spec.geoms if g.gtype != M.GT_CONVEX]
+    spec.gravity_off = 1            # franka_reach_MA.py:259
+    print("franka link masses:", {k: round(v, 3) for k, v in masses.items() if v > 0})
+    return spec
 
 
 HAND_FINGERTIPS = ["robot0:ffdistal", "robot0:mfdistal", "robot0:rfdistal", "robot0:lfdistal", "robot0:thdistal"]
@@ -149,7 +234,9 @@ def main():
     with open(os.path.join(out, "hand_objects.json"), "w") as f:
         json.dump(objs, f, indent=1)
     print("hand objects:", {k: (v["type"], v["size"], round(v["mass"], 5)) for k, v in objs.items()})
-    for s in (ant, hum, cp, sh):
+    fr = franka_panda()
+    fr.to_json(FRANKA_JSON)
+    for s in (ant, hum, cp, sh, fr):
         print(f"{s.name}: nodes={len(s.nodes)} dofs={s.num_dofs} bodies={len(s.bodies)} geoms={len(s.geoms)} "
               f"pairs={len(s.pairs)} mass={s.total_mass():.4f} sensors={s.sensors}")
 
