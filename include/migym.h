@@ -542,8 +542,15 @@ int mg_dynamics_refresh(mg_sim* sim, void* stream);
  *   out = clamp(u, -effort_limit, effort_limit)
  * with M the leading arm_dofs block of the full tree's mass matrix (the gripper's inertia included) and J the
  * arm_dofs leading columns of body jac_body's Jacobian rows, both computed in the kernel from the bound state (no J
- * or M goes through memory) unless jac_in / mm_in inject them.  M and A are factored by Cholesky; an actor whose
- * factorisation fails (a non-positive pivot: a singular pose, a massless model) gets zeros, never NaN. */
+ * or M goes through memory) unless jac_in / mm_in inject them.  M and A are factored by Cholesky, in double on the
+ * fp32 inputs (the torques are rounded to fp32: the solve itself loses no digits to cond(A)); an actor whose
+ * factorisation fails gets exactly 0 in every written column, never NaN or a garbage torque, and no other actor is
+ * affected.  A factorisation fails when a pivot s_j = X_jj - sum_k L_jk^2 (X = M or A) is not above 4.4e-5 X_jj: a
+ * singular or indefinite M (a massless model, a non-positive diagonal entry, a NaN), and any A that is singular to
+ * working precision -- a singular pose, a J with a zero or repeated row, and every call with arm_dofs < 6 (J then
+ * has rank < 6 and A is structurally singular: such calls return zeros).  The threshold is relative because
+ * the fp32 pivot of a singular matrix has a random sign; it sits 13 x above the largest spurious ratio measured on
+ * singular A and 13 x below the smallest true pivot ratio of the well-posed test poses (DESIGN.md s. 10). */
 typedef struct mg_osc_args {
   int32_t arm_dofs;          /* 1..7: the leading DOFs that are controlled */
   int32_t jac_body;          /* body whose Jacobian rows are used (1 <= jac_body < nB) */

@@ -289,90 +289,109 @@ __device__ __forceinline__ float floor_mod(float x, float y) {
 // The controller's dense algebra for one actor, in registers, on M (7 x 7) and J (6 x 7) padded past arm_dofs with
 // the identity / zeros (the padded DOFs then get zero torque and leave the others unchanged):
 //   M = L L^T, Y = L^-1 J^T, A = Y^T Y = J M^-1 J^T = G G^T, u = J^T A^-1 (w - J un) + M un
-// (the null-space term in its M^-1-free form, migym.h).  Returns false on a non-positive pivot.
+// (the null-space term in its M^-1-free form, migym.h).  The solve runs in double on the fp32 M, J, w and un and rounds
+// the torques to fp32: in fp32 it lost cond(A) eps32 of them (at cond(A) = 4.06e4 on the 17-node serial-arm tree, 0.16
+// N m of 614, 6.2 x the worst error of fp32 LU inverses on the same inputs), in double its error is the inputs' and the
+// output's rounding alone.  Returns false when a pivot of either factorisation fails the relative test
+// s_j > kPivotTol X_jj (X = M or A; a NaN fails it, and so does every pivot of a diagonal entry <= 0, since
+// s_j <= X_jj): the caller then writes zeros.  An absolute test s_j > 0 does not separate a singular matrix from a
+// regular one: the exact pivot is 0 and the computed one has a random sign (with J of rank arm_dofs < 6, A = Y^T Y has
+// rank arm_dofs; the fp32 Cholesky passed s > 0 on every pivot for 39 of 66 poses at arm_dofs = 5 on the MI355X, and
+// an emulation in double does so for 31).
+//
+// kPivotTol, from two CPU measurements on the cases of tests/test_gpu_dynamics.py (tests/test_dynamics_host.py
+// repeats both): (a) the largest first spurious pivot ratio |s_j| / A_jj of an FMA-free emulation of this function on
+// the structurally singular cases (arm_dofs 3 and 5 on the serial-arm tree, 66 poses each) is 8.2e-7 in fp32, the
+// precision of the inputs (3.3e-6 with a 4 x margin for the compiler's FMA contraction), and 1.4e-15 in double, the
+// working precision; (b) the smallest true pivot ratio, in fp64, over every well-posed case the tests use is 5.97e-4
+// (A on the arm_dofs = 6 tree; 1.02e-3 for A and 1.69e-2 for M on both Franka goldens, 0.38 for M on the tree).
+// 4.4e-5 is the geometric mean of the fp32 figure and (b): 13 x above the one, 13 x below the other.  It is held
+// against the fp32 figure because a pivot ratio is no better known than the fp32 inputs allow.
+constexpr float kPivotTol = 4.4e-5f;
 __device__ __forceinline__ bool osc_solve(const float (&M)[kOscMax][kOscMax], const float (&J)[6][kOscMax],
                                           const float (&w)[6], const float (&un)[kOscMax], float (&u)[kOscMax]) {
+  using T = double;   // the solve's working precision (inputs and torques stay fp32)
   constexpr int N = kOscMax;
   bool ok = true;
-  float L[N][N], di[N];
+  T L[N][N], di[N];
 #pragma unroll
   for (int j = 0; j < N; j++) {
-    float s = M[j][j];
+    T s = M[j][j];
 #pragma unroll
     for (int k = 0; k < j; k++) s -= L[j][k] * L[j][k];
-    ok = ok && (s > 0.0f);
-    const float d = sqrtf(fmaxf(s, 1e-30f));
-    di[j] = 1.0f / d;
+    ok = ok && (s > T(kPivotTol) * M[j][j]);
+    const T d = sqrt(fmax(s, T(1e-30)));
+    di[j] = T(1) / d;
 #pragma unroll
     for (int i = j + 1; i < N; i++) {
-      float t = M[i][j];
+      T t = M[i][j];
 #pragma unroll
       for (int k = 0; k < j; k++) t -= L[i][k] * L[j][k];
       L[i][j] = t * di[j];
     }
   }
-  float Y[N][6];
+  T Y[N][6];
 #pragma unroll
   for (int c = 0; c < 6; c++)
 #pragma unroll
     for (int i = 0; i < N; i++) {
-      float s = J[c][i];
+      T s = J[c][i];
 #pragma unroll
       for (int k = 0; k < i; k++) s -= L[i][k] * Y[k][c];
       Y[i][c] = s * di[i];
     }
-  float A[6][6];
+  T A[6][6];
 #pragma unroll
   for (int a = 0; a < 6; a++)
 #pragma unroll
     for (int b = 0; b <= a; b++) {
-      float s = 0.0f;
+      T s = 0;
 #pragma unroll
       for (int k = 0; k < N; k++) s += Y[k][a] * Y[k][b];
       A[a][b] = s;
     }
-  float G[6][6], gi[6];
+  T G[6][6], gi[6];
 #pragma unroll
   for (int j = 0; j < 6; j++) {
-    float s = A[j][j];
+    T s = A[j][j];
 #pragma unroll
     for (int k = 0; k < j; k++) s -= G[j][k] * G[j][k];
-    ok = ok && (s > 0.0f);
-    const float d = sqrtf(fmaxf(s, 1e-30f));
-    gi[j] = 1.0f / d;
+    ok = ok && (s > T(kPivotTol) * A[j][j]);
+    const T d = sqrt(fmax(s, T(1e-30)));
+    gi[j] = T(1) / d;
 #pragma unroll
     for (int i = j + 1; i < 6; i++) {
-      float t = A[i][j];
+      T t = A[i][j];
 #pragma unroll
       for (int k = 0; k < j; k++) t -= G[i][k] * G[j][k];
       G[i][j] = t * gi[j];
     }
   }
-  float z[6];
+  T z[6];
 #pragma unroll
   for (int a = 0; a < 6; a++) {   // g = w - J un, forward substitution in place
-    float s = w[a];
+    T s = w[a];
 #pragma unroll
-    for (int k = 0; k < N; k++) s -= J[a][k] * un[k];
+    for (int k = 0; k < N; k++) s -= T(J[a][k]) * un[k];
 #pragma unroll
     for (int k = 0; k < a; k++) s -= G[a][k] * z[k];
     z[a] = s * gi[a];
   }
 #pragma unroll
   for (int a = 5; a >= 0; a--) {
-    float s = z[a];
+    T s = z[a];
 #pragma unroll
     for (int k = a + 1; k < 6; k++) s -= G[k][a] * z[k];
     z[a] = s * gi[a];
   }
 #pragma unroll
   for (int i = 0; i < N; i++) {
-    float s = 0.0f;
+    T s = 0;
 #pragma unroll
-    for (int k = 0; k < N; k++) s += M[i][k] * un[k];
+    for (int k = 0; k < N; k++) s += T(M[i][k]) * un[k];
 #pragma unroll
     for (int a = 0; a < 6; a++) s += J[a][i] * z[a];
-    u[i] = s;
+    u[i] = (float)s;
   }
   return ok;
 }

@@ -1,5 +1,7 @@
 """Host-side checks of the dynamics-tensor feature (no GPU): the hull mass integration behind the Franka fixture, the
-fixture table itself, the OSC golden's internal consistency, and the new C-ABI exports."""
+fixture table itself, the OSC goldens' internal consistency, the new C-ABI exports, the oracle against an independent
+fp64 formula on the synthetic trees, the numpy controller against the reference's own method, and the two
+measurements behind the controller's pivot tolerance."""
 import ctypes as C
 import os
 import sys
@@ -92,3 +94,163 @@ def test_dynamics_entry_points_are_exported():
     # argument checks that need no device: a null sim
     assert l.mg_dynamics_refresh(None, None) == -1 and b"mg_dynamics_refresh" in l.mg_last_error()
     assert l.mg_osc_torques(None, None, None) == -1 and b"mg_osc_torques" in l.mg_last_error()
+
+
+# ------------------------------------------------------------------------------------------------ synthetic trees
+@pytest.mark.parametrize("name", list(R.TREES))
+def test_oracle_matches_the_independent_formula_on_trees(name):
+    """The oracle's CRBA mass matrix and velocity-column Jacobian against the plain fp64 restatement from the
+    definition (no shared code), on 6 random states per tree: within 1e-5 (max |dM| / max diag M, max |dJ|), which
+    is 100 x under the GPU tolerance; the difference is the oracle's fp32 rounding of its inputs.
+    Measured: branched17 1.1e-7 / 1.5e-7, branched33x 2.6e-7 / 5.0e-7, branched40 2.1e-7 / 3.4e-7,
+    chain40 7.7e-7 / 1.4e-6."""
+    spec = R.tree(name)
+    cfg = R.TREES[name]
+    assert len(spec.nodes) == cfg["num_nodes"] and len(spec.bodies) == cfg["num_nodes"] + cfg.get("extra_bodies", 0)
+    assert len(spec.bodies) <= M.MAX_BODIES and spec.nodes[0].jtype == M.JT_FIXED
+    assert all(0 <= n.parent < i and i - n.parent <= 6 for i, n in enumerate(spec.nodes) if i)
+    if cfg.get("chain"):
+        assert all(n.parent == i - 1 for i, n in enumerate(spec.nodes))
+    else:
+        assert any(n.parent != i - 1 for i, n in enumerate(spec.nodes) if i), "a branched tree"
+    root, q, Mo, Jo = R.tree_case(name, 6)
+    off = R.off_chain_mask(spec)
+    assert cfg.get("chain") or off[1:].any()
+    eM = eJ = 0.0
+    for a in range(6):
+        Mi, Ji = R.independent_mass_matrix_and_jacobian(spec, root[a], q[a])
+        eM = max(eM, np.abs(Mo[a] - Mi).max() / np.diag(Mi).max())
+        eJ = max(eJ, np.abs(Jo[a] - Ji).max())
+        assert np.linalg.eigvalsh(Mo[a]).min() > 0 and np.linalg.eigvalsh(Mi).min() > 0
+        assert np.abs(Mo[a] - Mo[a].T).max() <= 1e-12 * np.abs(Mo[a]).max()
+        for J in (Jo[a], Ji):
+            assert (J.transpose(0, 2, 1)[off] == 0.0).all(), "off-chain Jacobian entries are exact zeros"
+    print(f"{name}: max |M_orc - M_ind| / max diag = {eM:.3g}, max |J_orc - J_ind| = {eJ:.3g}")
+    assert eM <= 1e-5 and eJ <= 1e-5
+
+
+def test_tree_generator_reaches_the_edges():
+    """what the table in the tree cases promises: a second / third round of the lane loops, mask bits >= 32, interior
+    slides, several bodies on one node"""
+    s17, s33, c40 = R.tree("branched17"), R.tree("branched33x"), R.tree("chain40")
+    assert len(s17.nodes) == 17 and len(s33.nodes) == 33 and len(s33.bodies) == 40 == M.MAX_BODIES
+    assert len(R.ancestors(c40, 39)) == 39
+    assert any(max(R.ancestors(s33, b.node), default=0) >= 32 for b in s33.bodies)
+    nodes = [b.node for b in s33.bodies]
+    assert len(set(nodes)) < len(nodes) and nodes[:33] == list(range(33))
+    for s in (s17, s33, c40, R.tree("branched40"), R.tree("arm17")):
+        jt, par = [n.jtype for n in s.nodes], [n.parent for n in s.nodes]
+        assert any(jt[i] == M.JT_HINGE and jt[par[i]] == M.JT_SLIDE for i in range(1, len(jt)))
+        assert any(jt[i] == M.JT_SLIDE and jt[par[i]] == M.JT_HINGE for i in range(1, len(jt)))
+        assert M.pack_model(s)["num_nodes"] == len(s.nodes)
+    arm = R.tree("arm17")
+    assert R.ancestors(arm, arm.bodies[R.ARM_BODY].node)[::-1] == [1, 2, 3, 4, 5, 6]
+
+
+# ------------------------------------------------------------------------------------------------ OSC restatement
+def _golden_osc(g, limit, dtype=np.float64):
+    n = g["q"].shape[0]
+    kp = np.broadcast_to(g["kp"], (6,)).astype(np.float64)
+    kpn = np.broadcast_to(g["kp_null"], (7,)).astype(np.float64)
+    kd = g["kd"] if "kd" in g else 2 * np.sqrt(kp)
+    kdn = g["kd_null"] if "kd_null" in g else 2 * np.sqrt(kpn)
+    assert n == 64
+    return R.osc_reference(g["mm"], g["j_eef"], g["q"][:, :7], g["qd"][:, :7], g["dpose"], g["eef_vel"], kp, kd, kpn,
+                           kdn, g["default_dof_pos"][:7], limit, dtype)
+
+
+def test_osc_reference_matches_the_golden(golden):
+    """the numpy restatement against the reference's own method, both fp64 on identical inputs: within 1e-3 x ref_err
+    (two fp64 inverse routines at cond <= 5e4 and |u| ~ 1e2).  Measured: 4.2e-5 x ref_err, unclamped and clamped."""
+    g = golden
+    free = np.abs(_golden_osc(g, None) - g["u_ref64_free"]).max() / float(g["ref_err"])
+    clamped = np.abs(_golden_osc(g, g["effort_limit"][:7]) - g["u_ref64"]).max() / float(g["ref_err"])
+    print(f"osc_reference vs osc_franka.npz: {free:.3g} x ref_err unclamped, {clamped:.3g} x clamped")
+    assert free <= 1e-3 and clamped <= 1e-3
+    # its fp32 run errs like the reference's fp32 run (two fp32 algorithms: same order of magnitude)
+    _, err32 = _golden_osc(g, None, np.float32)
+    assert 0.1 * float(g["ref_err"]) <= err32 <= 10 * float(g["ref_err"])
+
+
+def test_osc_edges_golden(golden):
+    """tests/golden/osc_franka_edges.npz: same actors, J and M as osc_franka.npz; distinct gains, kd != 2 sqrt(kp), a
+    wrap that fires in both directions for every joint.  osc_reference within 1e-3 x its ref_err.
+    Measured: 1.9e-4 x ref_err (ref_err 9.58e-4 N m)."""
+    e = dict(np.load(R.OSC_EDGES_NPZ))
+    for k in ("mm", "j_eef", "qd", "dpose", "eef_vel", "root_states"):
+        assert np.array_equal(e[k], golden[k]), k
+    assert np.array_equal(e["q_base"], golden["q"]) and np.isinf(e["effort_limit"]).all()
+    assert e["u_ref32_free"].dtype == np.float32 and e["u_ref64_free"].dtype == np.float64
+    for k, m in (("kp", 6), ("kd", 6), ("kp_null", 7), ("kd_null", 7)):
+        assert e[k].shape == (m,) and len(set(e[k].tolist())) == m, k
+    assert np.abs(e["kd"] - 2 * np.sqrt(e["kp"])).min() > 0.04
+    assert np.abs(e["kd_null"] - 2 * np.sqrt(e["kp_null"])).min() > 0.04
+    q, d = e["q"][:, :7].astype(np.float64), e["default_dof_pos"][:7].astype(np.float64)
+    # the same pose (every arm joint is a hinge): q differs from the base q by whole turns, to fp32 rounding
+    assert np.abs(q - (e["q_base"][:, :7] + 2 * np.pi * e["turns"])).max() <= 5e-7
+    assert R.wrap_margin(d, q).min() >= 1e-3
+    x = d - q
+    wrapped = np.mod(x + np.pi, 2 * np.pi) - np.pi
+    up, down = wrapped - x > 1.0, wrapped - x < -1.0
+    assert up.any(0).all() and down.any(0).all(), "the wrap fires in both directions for every joint"
+    assert x.min() < -np.pi and x.max() > np.pi and np.abs(x).max() < 3 * np.pi
+    ref_err = np.abs(e["u_ref32_free"].astype(np.float64) - e["u_ref64_free"]).max()
+    assert float(e["ref_err"]) == ref_err and 0 < ref_err < 1e-2
+    ratio = np.abs(_golden_osc(e, None) - e["u_ref64_free"]).max() / ref_err
+    print(f"osc_reference vs osc_franka_edges.npz: {ratio:.3g} x ref_err")
+    assert ratio <= 1e-3
+
+
+def test_arm_tree_cases_are_well_posed_and_singular_as_intended():
+    """The controller cases on the serial-arm tree, from fp64 figures alone: arm_dofs = 6 is well posed
+    (cond(J M^-1 J^T) <= 5e4 for every actor); arm_dofs = 3 and 5 make A structurally singular (rank arm_dofs) with a
+    well-conditioned leading block (pivot ratios >= 1e-2).  Measured: cond max 4.06e4; leading ratios 0.145, 0.207."""
+    root, q, qd, dpose, eef, Mo, Jo = R.arm_case()
+    n = len(q)
+    assert n == R.TREE_ACTORS
+    cond = max(np.linalg.cond(Jo[a][:, :6] @ np.linalg.solve(Mo[a][:6, :6], Jo[a][:, :6].T)) for a in range(n))
+    print(f"arm tree, arm_dofs 6: cond(J M^-1 J^T) max {cond:.4g}")
+    assert cond <= 5e4
+    for k in (3, 5):
+        lead = 1.0
+        for a in range(n):
+            A = Jo[a][:, :k] @ np.linalg.solve(Mo[a][:k, :k], Jo[a][:, :k].T)
+            assert np.linalg.matrix_rank(A, tol=1e-9 * np.abs(A).max()) == k
+            rM, rA = R.osc_pivot_ratios(Mo[a][:k, :k], Jo[a][:, :k])
+            lead = min(lead, rM.min(), rA[:k].min())
+        print(f"arm tree, arm_dofs {k}: smallest leading pivot ratio {lead:.3g}")
+        assert lead >= 1e-2
+
+
+def test_pivot_tolerance_separates_singular_from_well_posed():
+    """The two measurements behind kPivotTol (csrc/dynamics_tensors.hpp), repeated: (a) the largest first spurious
+    pivot ratio of an FMA-free emulation of osc_solve on the structurally singular cases, x 4 for contraction, in
+    fp32 (the precision of the solve's inputs, and of the solve itself before it moved to double) and in double (the
+    solve's working precision); (b) the smallest true fp64 pivot ratio over every well-posed case the GPU tests use.
+    The tolerance sits 10 x clear of both.  Measured: (a) 8.23e-7 in fp32 (x 4: 3.3e-6), 1.4e-15 in double,
+    (b) 5.97e-4; under the absolute test s > 0 the fp32 emulation accepts 1 of 66 singular actors at arm_dofs 3 and 38
+    of 66 at arm_dofs 5, the double one 1 and 31."""
+    src = open(os.path.join(ROOT, "isaacgymenvs-ma_amd", "csrc", "dynamics_tensors.hpp")).read()
+    tau = float(src.split("constexpr float kPivotTol = ")[1].split("f;")[0])
+    root, q, qd, dpose, eef, Mo, Jo = R.arm_case()
+    n, f32 = len(q), np.float32
+    a_max, accepted, a_max64, accepted64 = 0.0, {}, 0.0, {}
+    for k in (3, 5):
+        accepted[k] = accepted64[k] = 0
+        for a in range(n):
+            M32, J32 = Mo[a][:k, :k].astype(f32), Jo[a][:, :k].astype(f32)
+            rM, rA = R.osc_pivot_ratios(M32, J32, f32)
+            a_max = max(a_max, abs(rA[k]))
+            accepted[k] += bool((rM > 0).all() and (rA > 0).all())
+            rM, rA = R.osc_pivot_ratios(M32, J32, np.float64)   # the kernel: fp32 inputs, the solve in double
+            a_max64 = max(a_max64, abs(rA[k]))
+            accepted64[k] += bool((rM > 0).all() and (rA > 0).all())
+    b_min = min(min(x.min() for x in R.osc_pivot_ratios(Mo[a][:6, :6], Jo[a][:, :6])) for a in range(n))
+    for path in (R.OSC_NPZ, R.OSC_EDGES_NPZ):
+        g = np.load(path)
+        b_min = min(b_min, min(min(x.min() for x in R.osc_pivot_ratios(g["mm"][a], g["j_eef"][a])) for a in range(64)))
+    print(f"(a) largest spurious pivot ratio {a_max:.3g} (x 4 = {4 * a_max:.3g}); (b) smallest true ratio {b_min:.3g}; "
+          f"kPivotTol {tau:.3g}; s > 0 would accept {accepted} of {n}; in double: (a) {a_max64:.3g}, s > 0 would "
+          f"accept {accepted64}")
+    assert accepted[5] > 0, "the absolute test does let singular actors through (what the relative test is for)"
+    assert 10 * 4 * max(a_max, a_max64) <= tau <= b_min / 10
