@@ -394,8 +394,13 @@ static void mass_matrix(const mg_model* m, const kin* k, real h, real* M, const 
   }
 }
 
-/* bias forces C(q,v) incl. gravity (RNEA with qdd = 0) and the link damping couples c I_w w (cd = c) */
-static void bias_forces(const mg_model* m, const kin* k, const astate* s, const real* g, real* C, real cd) {
+/* bias forces C(q,v) incl. gravity (RNEA with qdd = 0) and the link damping couples (cd = c, h the substep).  The
+ * couple is implicit in the link's angular velocity at the end of the substep, -c I_w (w + h dw/dt), and dw/dt =
+ * J qdd + dJ/dt qd: mass_matrix carries h c I_w for the first part, the second (the velocity-product acceleration A,
+ * which is all of dw/dt at qdd = 0) belongs here -- as the kernel's ABA has it, whose articulated inertias carry
+ * h c I_w and multiply the whole link acceleration.  Without it the step is short by h c I_w A: second order, and
+ * at gym's default damping of 0.5 / s worth 1e-4 of a joint rate per substep on a tumbling tree. */
+static void bias_forces(const mg_model* m, const kin* k, const astate* s, const real* g, real* C, real cd, real h) {
   int nn = m->num_nodes, nv = nv_of(m); /* C has at least nv entries */
   real A[MAXN][6], f[MAXN][6];
   for (int c = 0; c < 6; c++) A[0][c] = 0;
@@ -419,7 +424,8 @@ static void bias_forces(const mg_model* m, const kin* k, const astate* s, const 
     for (int a = 0; a < 3; a++) { f[i][a] = IA[a] + vIV[a] - n[a]; f[i][3 + a] = IA[3 + a] + vIV[3 + a] - mg[a]; }
     if (cd != 0.0) {
       real Iww[3];
-      matvec3((real(*)[3])k->Iw[i], k->V[i], Iww);
+      const real wn[3] = {k->V[i][0] + h * A[i][0], k->V[i][1] + h * A[i][1], k->V[i][2] + h * A[i][2]};
+      matvec3((real(*)[3])k->Iw[i], wn, Iww);
       for (int a = 0; a < 3; a++) f[i][a] += cd * Iww[a];
     }
   }
@@ -2514,7 +2520,7 @@ static void substep(const mg_model* m, const mg_sim_params* p, astate* s, const 
     }
   }
   mass_matrix(m, &k, h, M, diag, nvt, h * m->link_ang_damping);
-  bias_forces(m, &k, s, g, C, m->link_ang_damping);
+  bias_forces(m, &k, s, g, C, m->link_ang_damping, h);
   real nu[MAXV], rhs[MAXV];
   for (int c = 0; c < 6 && !m->fixed_base; c++) nu[c] = s->nu0[c];
   for (int i = 1; i < nn; i++) nu[dof_col(m, i)] = s->qd[i];
@@ -3076,7 +3082,7 @@ int orc_free_acceleration(const mg_model* m, const mg_sim_params* p, const float
   int nv = nv_of(m);
   real h = p->dt / p->substeps, M[MAXV * MAXV], C[MAXV], g[3] = {p->gravity[0], p->gravity[1], p->gravity[2]};
   mass_matrix(m, &k, h, M, 0, nv, h * m->link_ang_damping);
-  bias_forces(m, &k, &s, g, C, m->link_ang_damping);
+  bias_forces(m, &k, &s, g, C, m->link_ang_damping, h);
   if (cholesky(M, nv) != 0) return -1;
   for (int c = 0; c < nv; c++) qacc_out[c] = -C[c];
   for (int i = 1; i < m->num_nodes; i++)

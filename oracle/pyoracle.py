@@ -41,6 +41,7 @@ def lib():
         l.orc_mass_matrix.argtypes = [P, C.POINTER(_abi.SimParams), P, P, P]
         l.orc_free_acceleration.argtypes = [P, C.POINTER(_abi.SimParams), P, P, P, P]
         l.orc_contacts.argtypes = [P, C.POINTER(_abi.SimParams), P, P, P, C.c_int32]
+        l.orc_contacts_full.argtypes = [P, C.POINTER(_abi.SimParams), P, P, P, C.c_int32]
         l.orc_rigid_body_states.argtypes = [P, P, P, P]
         l.orc_compute_observations.argtypes = [C.POINTER(_abi.TaskParams), C.c_int32] + [P] * 10
         l.orc_compute_reward.argtypes = [C.POINTER(_abi.TaskParams), C.c_int32] + [P] * 7
@@ -127,6 +128,14 @@ def contacts(model_np, sp, root13, dof2, cap=64):
     out = np.zeros(9 * cap)
     n = lib().orc_contacts(model_np.ctypes.data, C.byref(sp), p(f32(root13)), p(f32(dof2)), p(out), cap)
     return out[: 9 * n].reshape(n, 9)
+
+
+def contacts_full(model_np, sp, root13, dof2, cap=64):
+    """the contact candidates with both geoms: rows (nodeA, geomA, nodeB, geomB, p(3), n(3), d); nodeB / geomB < 0
+    against the ground"""
+    out = np.zeros(11 * cap)
+    n = lib().orc_contacts_full(model_np.ctypes.data, C.byref(sp), p(f32(root13)), p(f32(dof2)), p(out), cap)
+    return out[: 11 * n].reshape(n, 11)
 
 
 def box_box_edge(c, R, h, hb, off):

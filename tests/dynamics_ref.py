@@ -62,7 +62,8 @@ OSC_EDGES_NPZ = os.path.join(GOLDEN, "osc_franka_edges.npz")
 
 
 # ------------------------------------------------------------------------------------------------ synthetic trees
-def random_tree(num_nodes, seed, chain=False, extra_bodies=0, chain_prefix=0):
+def random_tree(num_nodes, seed, chain=False, extra_bodies=0, chain_prefix=0, physics=False, free_base=False,
+                num_geoms=0, num_pairs=0, num_sensors=0, boxes=True):
     """A synthetic fixed-base articulation that reaches what the Franka chain and Cartpole cannot: branching, more
     than 16 / 32 nodes, slides in the interior, body origins off the joint anchor, several bodies on one node.
 
@@ -72,7 +73,18 @@ def random_tree(num_nodes, seed, chain=False, extra_bodies=0, chain_prefix=0):
     U(-0.05, 0.05)^3, a random SPD inertia about the COM (0.01 A A^T + 0.005 I), a mass in U(0.2, 2) and an armature
     in U(0, 0.05); limits are +-1.  One body per node at a random origin in U(-0.1, 0.1)^3 of the node frame, plus
     ``extra_bodies`` more on random nodes (the fixed-joint case: a non-identity body_node map).  No geoms, pairs,
-    actuators or sensors; gravity off."""
+    actuators or sensors; gravity off.
+
+    The keyword options after ``chain_prefix`` make the tree step-ready (tests/tree_physics_ref.py); they draw from a
+    generator of their own, so the tree above is the same with and without them.  ``physics``: gravity on, joint
+    damping in U(0.05, 0.5), stiffness in U(0, 5), frictionloss in U(0.05, 0.3) on every fourth DOF.  ``free_base``:
+    node 0 is a free joint (its mass and inertia are the ones drawn above).  ``num_geoms`` geoms cycling sphere,
+    capsule, box over the nodes in a random order (distinct nodes until every node has one), a centre in
+    U(-0.03, 0.03)^3 of the node frame and a rotation of up to 0.3 rad about a random axis, colliding with the ground
+    only (``boxes`` False: spheres and capsules alone, the kernel's one-pass ground path).  ``num_pairs`` self-collision pairs of sphere / capsule geoms whose nodes are neither equal nor parent and
+    child: those whose bounding spheres are apart at the zero pose, the nearest first (random poses then put some in
+    contact, few of them deep), then the ones that overlap there, the shallowest first.  ``num_sensors`` force sensors on leaf bodies (as many as the
+    tree has leaves, at most)."""
     rng = np.random.default_rng(seed)
 
     def unit(k):
@@ -106,8 +118,78 @@ def random_tree(num_nodes, seed, chain=False, extra_bodies=0, chain_prefix=0):
     par = [n.parent for n in nodes]
     assert any(jt[i] == M.JT_HINGE and jt[par[i]] == M.JT_SLIDE for i in range(1, num_nodes)), "no hinge below a slide"
     assert any(jt[i] == M.JT_SLIDE and jt[par[i]] == M.JT_HINGE for i in range(1, num_nodes)), "no slide below a hinge"
-    return M.ModelSpec(name=f"tree{num_nodes}_{seed}", fixed_base=1, nodes=nodes, bodies=bodies, geoms=[], pairs=[],
+    spec = M.ModelSpec(name=f"tree{num_nodes}_{seed}", fixed_base=1, nodes=nodes, bodies=bodies, geoms=[], pairs=[],
                        actuators=[], dof_names=[n.name for n in nodes[1:]], gravity_off=1)
+    if physics or free_base or num_geoms or num_pairs or num_sensors:
+        _step_ready(spec, np.random.default_rng([seed, 1]), physics, free_base, num_geoms, num_pairs, num_sensors,
+                    boxes)
+    return spec
+
+
+def _step_ready(spec, rng, physics, free_base, num_geoms, num_pairs, num_sensors, boxes):
+    """random_tree's step options, in place"""
+    nn = len(spec.nodes)
+    if physics:
+        spec.gravity_off = 0
+        for i, nd in enumerate(spec.nodes[1:]):
+            nd.damping, nd.stiffness = float(rng.uniform(0.05, 0.5)), float(rng.uniform(0.0, 5.0))
+            if i % 4 == 2:
+                nd.frictionloss = float(rng.uniform(0.05, 0.3))
+    if free_base:
+        spec.fixed_base, spec.nodes[0].jtype = 0, M.JT_FREE
+    order = np.concatenate([rng.permutation(nn) for _ in range(-(-max(num_geoms, 1) // nn))])
+    for g in range(num_geoms):
+        gt = (M.GT_SPHERE, M.GT_CAPSULE, M.GT_BOX)[g % (3 if boxes else 2)]
+        size = {M.GT_SPHERE: [rng.uniform(0.03, 0.06), 0.0, 0.0],
+                M.GT_CAPSULE: [rng.uniform(0.02, 0.04), rng.uniform(0.04, 0.1), 0.0],
+                M.GT_BOX: rng.uniform(0.03, 0.08, 3).tolist()}[gt]
+        ax = rng.normal(size=3)
+        quat = M.quat_from_axis_angle(ax, rng.uniform(-0.3, 0.3))
+        nd = int(order[g])
+        spec.geoms.append(M.Geom(name=f"g{g}", gtype=gt, node=nd, body=nd, size=[float(v) for v in size],
+                                 pos=rng.uniform(-0.03, 0.03, 3).tolist(), quat=quat.tolist(),
+                                 filter=M.COLLIDE_GROUND))
+    if num_pairs:
+        root = np.array([0, 0, 0, 0, 0, 0, 1.0] + [0.0] * 6)
+        R, x = node_frames(spec, root, np.zeros(spec.num_dofs))
+        ctr = [x[g.node] + R[g.node] @ np.asarray(g.pos) for g in spec.geoms]
+        cand = []
+        for i, gi in enumerate(spec.geoms):
+            for j in range(i + 1, len(spec.geoms)):
+                gj = spec.geoms[j]
+                if M.GT_BOX in (gi.gtype, gj.gtype) or gi.node == gj.node:
+                    continue
+                if spec.nodes[gi.node].parent == gj.node or spec.nodes[gj.node].parent == gi.node:
+                    continue
+                reach = gi.size[0] + gi.size[1] + gj.size[0] + gj.size[1]   # the two bounding spheres
+                gap = float(np.linalg.norm(ctr[i] - ctr[j])) - reach
+                cand.append((gap if gap >= 0 else 1e3 - gap, i, j))
+        assert len(cand) >= num_pairs, f"only {len(cand)} candidate pairs"
+        spec.pairs = [[i, j] for _, i, j in sorted(cand)[:num_pairs]]
+    if num_sensors:
+        parents = {n.parent for n in spec.nodes}
+        spec.sensors = [i for i in range(1, nn) if i not in parents][:num_sensors]
+
+
+def node_frames(spec, root13, q):
+    """(R, x): world rotation and origin of every node frame, plain fp64 numpy; FK as include/migym.h states it: a
+    hinge has R = R_p R0 exp([axis] q), x = x_p + R_p t; a slide R = R_p R0, x = x_p + R_p t + (R_p R0 axis) q"""
+    root13, q = np.asarray(root13, np.float64), np.asarray(q, np.float64)
+    nn = len(spec.nodes)
+    R, x = [None] * nn, [None] * nn
+    R[0], x[0] = M.qmat(M.qnorm(root13[3:7])), root13[0:3].copy()
+    for i in range(1, nn):
+        n, p = spec.nodes[i], spec.nodes[i].parent
+        Rp0 = R[p] @ M.qmat(M.qnorm(n.r0))
+        ax = np.asarray(n.axis, np.float64)
+        if n.jtype == M.JT_HINGE:
+            K = _skew(ax)
+            R[i] = Rp0 @ (np.eye(3) + np.sin(q[i - 1]) * K + (1.0 - np.cos(q[i - 1])) * K @ K)
+            x[i] = x[p] + R[p] @ np.asarray(n.t)
+        else:
+            R[i] = Rp0
+            x[i] = x[p] + R[p] @ np.asarray(n.t) + (Rp0 @ ax) * q[i - 1]
+    return R, x
 
 
 def ancestors(spec, node):

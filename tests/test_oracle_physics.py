@@ -292,6 +292,53 @@ def test_free_link_angular_damping_decays_per_substep():
     np.testing.assert_allclose(root[0, 10:13], (3.0, -2.0, 1.0), rtol=1e-7)
 
 
+def test_link_angular_damping_is_implicit_in_the_whole_link_acceleration():
+    """Known answer of the link damping on a tumbling tree (gym's default angular_damping 0.5 / s).  The couple on
+    link i is -c I_w (w + h dw/dt) with dw/dt = Jw qdd + dJw/dt qd, so the oracle's free acceleration must satisfy
+    (M + h c sum Jw^T I_w Jw) qdd_c = M qdd_0 - c sum Jw^T I_w (w + h dJw/dt qd), with qdd_0 the undamped one and
+    everything on the right in plain numpy from the FK (dJw/dt qd of a link: the sum over its hinges of
+    w_parent x axis qd).  The oracle once left out the h dJw/dt qd part, which the kernel's ABA carries (its
+    articulated inertias hold h c I_w and multiply the whole link acceleration): GPU and oracle then parted by ~1e-4
+    of a joint rate per substep (tests/test_gpu_tree_physics.py found it)."""
+    import copy
+    import dynamics_ref as D
+    spec = D.random_tree(17, 1)
+    nd, c = spec.num_dofs, 0.5
+    sp = D.oracle_sim_params()
+    h = sp.dt / sp.substeps
+    rng = np.random.default_rng(3)
+    root, q = D.random_states(spec, 1, 5)
+    qd = rng.normal(0, 3.0, nd)
+    dof = np.stack([q[0], qd], 1).astype(np.float32)
+    q64, qd64 = dof[:, 0].astype(np.float64), dof[:, 1].astype(np.float64)
+    acc = {}
+    for cd in (0.0, c):
+        s = copy.deepcopy(spec)
+        s.angular_damping = cd
+        acc[cd] = O.free_acceleration(D.oracle_model(s), sp, root[0], dof)
+    Mq = D.oracle_mass_matrix(D.oracle_model(spec), root[0], q[0])
+    R, _ = D.node_frames(spec, root[0], q64)
+    K, rhs, rhs_without = np.zeros((nd, nd)), np.zeros(nd), np.zeros(nd)
+    w, wdot, Jw = [np.zeros(3)] * len(spec.nodes), [np.zeros(3)] * len(spec.nodes), [np.zeros((3, nd))] * len(spec.nodes)
+    for i in range(1, len(spec.nodes)):
+        n, p = spec.nodes[i], spec.nodes[i].parent
+        w[i], wdot[i], Jw[i] = w[p].copy(), wdot[p].copy(), Jw[p].copy()
+        if n.jtype == M.JT_HINGE:
+            a = R[i] @ np.asarray(n.axis)
+            wdot[i] = wdot[i] + np.cross(w[p], a) * qd64[i - 1]
+            w[i] = w[i] + a * qd64[i - 1]
+            Jw[i][:, i - 1] = a
+        i6 = n.inertia
+        Iw = R[i] @ np.array([[i6[0], i6[3], i6[4]], [i6[3], i6[1], i6[5]], [i6[4], i6[5], i6[2]]]) @ R[i].T
+        K += Jw[i].T @ Iw @ Jw[i]
+        rhs += Jw[i].T @ Iw @ (w[i] + h * wdot[i])
+        rhs_without += Jw[i].T @ Iw @ w[i]
+    lhs = (Mq + h * c * K) @ acc[c] - Mq @ acc[0.0]
+    scale = np.abs(c * rhs).max()
+    np.testing.assert_allclose(lhs, -c * rhs, atol=1e-6 * scale)
+    assert np.abs(lhs + c * rhs_without).max() > 1e-3 * scale   # the term is no rounding matter on this state
+
+
 def test_free_link_angular_velocity_is_capped_keeping_com_velocity():
     spec = free_link_spec(0.0, 10.0)
     spec.nodes[0].com = [0.1, 0.0, 0.0]          # COM off the origin: the cap keeps v_com, not v_o
