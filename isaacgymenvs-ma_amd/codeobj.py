@@ -7,6 +7,9 @@ DESIGN.md §3 Resources).  ``calls(so)`` lists every ``s_swappc_b64`` (a call) a
 return: only a callable function has one; long branches use s_setpc_b64 on other registers) in the device code, per code object, so build.py can fail
 the build and tests/test_code_objects.py can assert on the shipped library.
 
+``diff(old_so, new_so)`` compares two builds' device code (section bytes and disassembly, per code object): the
+check for a source change that must leave the machine code as it was (tools/codeobj_diff.py).
+
 The fat binary is read without the ROCm bundler: the ELF section ``.hip_fatbin`` holds one clang offload
 bundle per translation unit ("__CLANG_OFFLOAD_BUNDLE__", entry count, then (offset, size, triple) per entry),
 and the gfx950 entry of each is an AMDGPU ELF that ``llvm-objdump -d`` disassembles.
@@ -48,8 +51,10 @@ def have_objdump():
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
-def _section(path, name):
-    d = open(path, "rb").read()
+def _section(path, name, d=None):
+    """section `name` of the ELF64 file at `path` (or of the image `d`, `path` then only names it in errors)"""
+    if d is None:
+        d = open(path, "rb").read()
     if d[:4] != b"\x7fELF" or d[4] != 2:
         raise ValueError(f"{path}: not an ELF64 file")
     shoff, = struct.unpack_from("<Q", d, 0x28)
@@ -81,22 +86,34 @@ def device_code_objects(so, arch="gfx950"):
     return out
 
 
+def _disassemble(co, arch):
+    """``llvm-objdump -d`` of one code object (bytes), without the header lines that carry the file's name"""
+    with tempfile.TemporaryDirectory() as td:
+        f = os.path.join(td, "co.o")
+        with open(f, "wb") as fh:
+            fh.write(co)
+        txt = subprocess.run([_objdump(), "-d", f"--mcpu={arch}", f], capture_output=True, text=True, check=True).stdout
+    return [line for line in txt.splitlines() if "file format" not in line]
+
+
+def _functions(lines):
+    """{function: its lines} of a disassembly"""
+    fns, fn = {}, "?"
+    for line in lines:
+        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+        if m:
+            fn = m.group(1)
+        fns.setdefault(fn, []).append(line)
+    return fns
+
+
 def calls(so, arch="gfx950"):
     """[(code object index, function, instruction)] for every call / return in the device code"""
     found = []
-    with tempfile.TemporaryDirectory() as td:
-        for k, co in enumerate(device_code_objects(so, arch)):
-            f = os.path.join(td, f"co{k}.o")
-            with open(f, "wb") as fh:
-                fh.write(co)
-            txt = subprocess.run([_objdump(), "-d", f"--mcpu={arch}", f], capture_output=True, text=True,
-                                 check=True).stdout
-            fn = "?"
-            for line in txt.splitlines():
-                m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-                if m:
-                    fn = m.group(1)
-                elif "s_swappc_b64" in line or re.search(r"s_setpc_b64\s+s\[30:31\]", line):
+    for k, co in enumerate(device_code_objects(so, arch)):
+        for fn, lines in _functions(_disassemble(co, arch)).items():
+            for line in lines:
+                if "s_swappc_b64" in line or re.search(r"s_setpc_b64\s+s\[30:31\]", line):
                     # a call, or a return through the return address (s[30:31]): a callable function.  Long
                     # branches (s_getpc_b64 + add + s_setpc_b64 on other registers) are kernels' own jumps
                     found.append((k, fn, line.split()[0]))
@@ -110,3 +127,35 @@ def check_no_calls(so, arch="gfx950"):
         raise RuntimeError(f"{so}: the device code has real calls / returns (the team kernels must be fully "
                            f"inlined, DESIGN.md §3b): {fns[:8]}")
     return True
+
+
+def diff(old_so, new_so, arch="gfx950"):
+    """Compare the device code of two built libraries, code object by code object in .hip_fatbin order: the
+    ``.text`` and ``.rodata`` bytes (code and kernel descriptors) and the disassembly.  Returns (code objects
+    compared, [(code object index, sections whose bytes differ, functions whose disassembly differs)]); an empty
+    list is the same machine code, which is what a source change meant to move none has to show.  A function counts
+    as different when its instructions or their encodings do, not when it merely sits at another address behind
+    one that grew.  A code object that only one library has is listed with every function it holds."""
+    def body(lines):  # a function's instructions and encodings: without its header line and the address column
+        return [re.sub(r"// [0-9A-F]+:", "//", line) for line in lines[1:]]
+
+    def sect(co, name):
+        try:
+            return _section("code object", name, co)
+        except ValueError:
+            return b""
+
+    old, new = device_code_objects(old_so, arch), device_code_objects(new_so, arch)
+    out = []
+    for k in range(max(len(old), len(new))):
+        if k >= len(old) or k >= len(new):
+            only = old[k] if k < len(old) else new[k]
+            out.append((k, ["missing"], sorted(_functions(_disassemble(only, arch)))))
+            continue
+        secs = [n for n in (".text", ".rodata") if sect(old[k], n) != sect(new[k], n)]
+        a, b = _disassemble(old[k], arch), _disassemble(new[k], arch)
+        if secs or a != b:
+            fa, fb = _functions(a), _functions(b)
+            out.append((k, secs, sorted(f for f in set(fa) | set(fb)
+                                        if f not in fa or f not in fb or body(fa[f]) != body(fb[f]))))
+    return max(len(old), len(new)), out

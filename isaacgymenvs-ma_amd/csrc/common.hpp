@@ -9,13 +9,10 @@
 
 // the compact team layout (team_physics.hpp TeamLDSC): the 16- and 32-lane locomotion instances, whose
 // LDS then holds twelve waves per CU.  Its ABA slots are per tree level (kCompactLevelSlots nodes at one depth at most),
-// which the dispatcher checks against the model (dispatch.hpp MG_FITS)
-#ifndef MG_COMPACT_LDS
-#define MG_COMPACT_LDS 1
-#endif
+// which the dispatcher checks against the model (dispatch.hpp MG_FITS).  MIGYM_LAYOUT=classic turns it off at run time
 constexpr int kCompactLevelSlots = 8;
 constexpr bool mg_compact_layout(int T, int MN, int OBJ) {
-  return MG_COMPACT_LDS && (T == 16 || T == 32) && OBJ == 0 && MN <= 32;
+  return (T == 16 || T == 32) && OBJ == 0 && MN <= 32;
 }
 
 struct mg_sim {
@@ -46,7 +43,7 @@ struct mg_sim {
   unsigned* d_bq;      // lists: [2][kOrderBuckets] bucket counts, then the launch's finished-wave counter
   int* d_blist;        // lists: [2][kOrderBuckets][bq_cap] env indices per bucket
   int bq_cap;          // env units (n / order_unit)
-  int order_unit;      // actors per unit of the work order: an env's A agents (MG_SORT_WAVE_UNITS: a wave's teams)
+  int order_unit;      // actors per unit of the work order: an env's A agents
   int order_agents;    // the agents per env the order was sized for
   int* d_order;        // sort: (bq_cap) slot -> env unit
   unsigned char* d_cost;  // sort: (bq_cap) the last launch's row count per env unit (its agents' largest, <= 255)
@@ -66,12 +63,9 @@ struct mg_sim {
 constexpr int kOrderBuckets = 32;  // row-count classes of width kOrderWidth, descending (bucket 0: 62 rows and more)
 constexpr int kOrderWidth = 2;
 constexpr int kOrderOff = 0, kOrderLists = 1, kOrderSort = 2;
-#ifndef MG_SORT_REP
-#define MG_SORT_REP 8
-#endif
 // sort: copies of the bin totals (block b adds into copy b % kSortRep): the hot bins' device-scope atomics spread
 // over 8 words each (k_ohist 6.4 -> 4.8 us at 65,536 envs under the profiler; Ant 65,536 +0.3 %)
-constexpr int kSortRep = MG_SORT_REP;
+constexpr int kSortRep = 8;
 constexpr int kSortTot = kSortRep * 256;  // sort: the bin totals (zero before every sort: the step kernel that consumes
                                          // a sort's permutation clears them, MgOrder::tot_clear)
 struct MgOrder {
@@ -87,14 +81,9 @@ struct MgOrder {
   unsigned long long* clk;  // nullptr, or this launch's span slot (mg_kernel_span_begin)
   unsigned* tot_clear;      // sort: the bin totals, zeroed by block 0 of the step kernel (k_oscatter, their last reader,
                             // has finished: stream order), so the next sort starts from zero with no host-side state
-  int unit;                 // sort: actors per unit (consecutive actors, one permutation entry; divides a wave's teams)
+  int unit;                 // sort: actors per unit (consecutive actors, one permutation entry; divides a wave's teams):
+                            // always the env's agent count today (mg_sim_create; an MA env's agents stay together)
 };
-// sort units of one wave's consecutive envs (64 / T single-agent envs per unit, keyed by their largest row count):
-// every wave steps 64 / T consecutive envs, so the small per-env arrays keep their lines whole (VERDICT r5 item 3's
-// line-coherent units); 0: one env per unit (an MA env's agents together)
-#ifndef MG_SORT_WAVE_UNITS
-#define MG_SORT_WAVE_UNITS 0
-#endif
 
 namespace mgi {
 constexpr int kBlock = 64;

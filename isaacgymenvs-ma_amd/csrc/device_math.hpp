@@ -147,19 +147,9 @@ __device__ __forceinline__ Sym6 body_inertia(float m, V3 c, const float* Ic) {
 }
 // reciprocal / square root / inverse square root of the physics: the 1-ulp hardware instructions instead
 // of the correctly rounded sequences (~10 instructions each); the task layer keeps IEEE division
-// (MG_EXACT_RCP: the correctly rounded forms, a parity A/B only)
-#ifndef MG_EXACT_RCP
-#define MG_EXACT_RCP 0
-#endif
-#if MG_EXACT_RCP
-__device__ __forceinline__ float prcp(float x) { return 1.0f / x; }
-__device__ __forceinline__ float psqrt(float x) { return sqrtf(x); }
-__device__ __forceinline__ float prsq(float x) { return 1.0f / sqrtf(x); }
-#else
 __device__ __forceinline__ float prcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float psqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float prsq(float x) { return __builtin_amdgcn_rsqf(x); }
-#endif
 // sine and cosine of the physics' angles (joint angles in FK, the root's / object's half rotation per substep; five
 // pairs per lane and step).  HW: the hardware v_sin_f32 / v_cos_f32 on the argument in revolutions reduced to
 // [-1/2, 1/2] (a few instructions instead of the library's ~60; absolute error tools/trig_probe.hip), used by the
@@ -168,11 +158,11 @@ __device__ __forceinline__ float prsq(float x) { return __builtin_amdgcn_rsqf(x)
 // library's everywhere.
 //
 // poly_sincos: a polynomial pair (one Cody-Waite reduction by pi/2, Cephes' minimax polynomials on [-pi/4, pi/4]),
-// the physics' pair of the instances that are not 16-lane (MG_POLY_TRIG below).  Round 5's first form took the
+// the physics' pair of the instances that are not 16-lane (psincos below).  Round 5's first form took the
 // quadrant as (int)rint(x 2/pi) and its first GPU run faulted; its source was not kept.  This
 // form never converts a float to an integer: the quadrant is k - 4 floor(k / 4) in floating point and the result is
 // picked by float compares, so a NaN / infinite / huge x can only give a NaN / wrong value, never an address or a
-// branch target.  MG_POLY_TRIG=2 rebuilds the integer-quadrant form for the disassembly check
+// branch target.  int_quadrant rebuilds the integer-quadrant form from its description; no kernel takes it
 // (tests/test_trig_kat.py: host KAT of both forms over NaN, +-Inf, +-1e30, denormals and Cartpole-range angles).
 __host__ __device__ __forceinline__ void poly_sincos(float x, float* s, float* c, bool int_quadrant = false) {
   const float k = rintf(x * 0.636619772367581343f);  // nearest multiple of pi / 2
@@ -196,13 +186,9 @@ __host__ __device__ __forceinline__ void poly_sincos(float x, float* s, float* c
   *s = ns ? -sv : sv;
   *c = nc ? -cv : cv;
 }
-// the physics' pair outside the 16-lane instances (Humanoid, the hand, Cartpole): 1 = poly_sincos (round 6: GPU suite
-// green, 168 passed, the Humanoid fast-spin case included; same box, two passes, Humanoid 32,768 +1.0 %, ShadowHand
-// 4,096 +0.9 %, 16,384 +0.3 %, profiles/r06/ab_poly_trig.txt), 0 = the library's sinf / cosf, 2 = the integer-quadrant
-// form (disassembly check only)
-#ifndef MG_POLY_TRIG
-#define MG_POLY_TRIG 1
-#endif
+// the physics' pair: the hardware's (HW, the 16-lane instances) or poly_sincos (Humanoid, the hand, Cartpole; round 6,
+// against the library's sinf / cosf: GPU suite green, 168 passed, the Humanoid fast-spin case included; same box, two
+// passes, Humanoid 32,768 +1.0 %, ShadowHand 4,096 +0.9 %, 16,384 +0.3 %, profiles/r06/ab_poly_trig.txt)
 template <bool HW>
 __device__ __forceinline__ void psincos(float x, float* s, float* c) {
   if constexpr (HW) {
@@ -210,11 +196,8 @@ __device__ __forceinline__ void psincos(float x, float* s, float* c) {
     r = r - __builtin_rintf(r);
     *s = __builtin_amdgcn_sinf(r);
     *c = __builtin_amdgcn_cosf(r);
-  } else if constexpr (MG_POLY_TRIG != 0) {
-    poly_sincos(x, s, c, MG_POLY_TRIG == 2);
   } else {
-    *s = sinf(x);
-    *c = cosf(x);
+    poly_sincos(x, s, c);
   }
 }
 // tanh of the joint friction law: (1 - e) / (1 + e), e = exp(-2|x|) by the hardware exp2 (~7 instructions instead of

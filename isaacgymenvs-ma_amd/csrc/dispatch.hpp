@@ -8,10 +8,6 @@
 // contacts MC, geoms MG, self pairs MP, OBJ = the free object's type in hand-task envs (0: none; one
 // instance per object shape, so the block's kernel carries no egg / pen code).  The smallest
 // instance that fits the model is launched.
-// (occupancy experiments only: the 16-lane locomotion instance's contact capacity)
-#ifndef MG_ANT_MC
-#define MG_ANT_MC 16
-#endif
 // LAY (last field): the team layout.  1 = the compact layout at three waves per SIMD (TeamLDSC), taken for batches of
 // more than kCompactMinWaves waves; 0 = the classic layout at two waves per SIMD (TeamLDS) otherwise.  Twelve waves per
 // CU pay where the batch fills several rounds of them; a batch that fits one or two rounds of the classic kernel's
@@ -19,7 +15,7 @@
 // 128.6 vs 119.2 M; 32,768: 152.7 vs 176.8 M), so the two compact-capable capacities come in both layouts,
 // compact first.
 #define MG_INSTANCES(X)                                                                                                \
-  X(8, 4, 8, 4, 0, 0, 0) X(16, 9, MG_ANT_MC, 16, 0, 0, 1) X(16, 9, MG_ANT_MC, 16, 0, 0, 0) X(16, 16, 24, 24, 32, 0, 0)   \
+  X(8, 4, 8, 4, 0, 0, 0) X(16, 9, 16, 16, 0, 0, 1) X(16, 9, 16, 16, 0, 0, 0) X(16, 16, 24, 24, 32, 0, 0)                 \
   X(32, 24, 32, 24, 160, 0, 1) X(32, 24, 32, 24, 160, 0, 0) X(32, 32, 48, 48, 192, 0, 0) X(64, 40, 48, 48, 192, 0, 0)    \
   X(32, 25, 24, 24, 24, MG_GT_BOX, 0) X(32, 25, 24, 24, 24, MG_GT_CAPSULE, 0) X(32, 25, 24, 24, 24, MG_GT_ELLIPSOID, 0)
 #define MG_NUM_INST 11

@@ -556,10 +556,6 @@ int mg_sim_create(const mg_model* model, const mg_sim_params* params, int32_t nu
       return fail(MG_EINVAL, "mg_sim_create: nodes must be topologically ordered (parent < child)");
   if (params->substeps < 1 || params->dt <= 0.0f || params->max_contacts < 0)
     return fail(MG_EINVAL, "mg_sim_create: bad sim params");
-#ifdef MG_EXP_CLAMP_CONTACTS  // occupancy experiments only: the contact capacity clamped (never a shipped build)
-  const_cast<mg_sim_params*>(params)->max_contacts =
-      params->max_contacts < MG_EXP_CLAMP_CONTACTS ? params->max_contacts : MG_EXP_CLAMP_CONTACTS;
-#endif
   if ((params->solver_type != MG_SOLVER_PGS && params->solver_type != MG_SOLVER_TGS) || params->vel_iters < 0)
     return fail(MG_EINVAL, "mg_sim_create: solver_type must be MG_SOLVER_PGS or MG_SOLVER_TGS, vel_iters >= 0");
   // the exact hull-object candidates are computed before the tree phases (team_physics.hpp hull_stage), from
@@ -654,10 +650,6 @@ int mg_sim_create(const mg_model* model, const mg_sim_params* params, int32_t nu
     const int A = params->agents > 1 ? params->agents : 1;
     s->order_agents = A;
     s->order_unit = A;
-    if (MG_SORT_WAVE_UNITS && s->order_mode == kOrderSort && A == 1 && s->host_model.obj_type == 0) {
-      const int T = mgi::team_size(s->host_model, s->params.max_contacts), U = T > 0 ? 64 / T : 1;
-      if (U > 1 && num_envs % U == 0) s->order_unit = U;  // (a ragged batch keeps one env per unit)
-    }
     s->bq_cap = (num_envs + s->order_unit - 1) / s->order_unit;
     const size_t nu = (size_t)s->bq_cap, nb = (nu + 255) / 256;
     const bool ok = s->order_mode == kOrderLists

@@ -12,20 +12,16 @@
 #include "task.hpp"
 #include "team_physics.hpp"
 
-
-// waves per SIMD the register allocator targets (2: the 256-VGPR budget; an A/B variant may ask for 3, <= 168 VGPRs)
+// Build-time tunables (build.py --variant NAME -D ...; the supported set is listed in DESIGN.md §7).
+// waves per SIMD the register allocator targets (2: the 256-VGPR budget; a variant may ask for 3, <= 168 VGPRs)
 #ifndef MG_WAVES_PER_EU
 #define MG_WAVES_PER_EU 2
 #endif
-// ... and for the instances with the compact team layout (mg::TeamLDSC: Ant, MA-Ant), whose LDS holds 12 waves per CU
+// ... and for the instances with the compact team layout (mg::TeamLDSC: Ant, MA-Ant, Humanoid), whose LDS holds 12
+// waves per CU
 #ifndef MG_WAVES_COMPACT
 #define MG_WAVES_COMPACT 3
 #endif
-// the compact 32-lane instances (Humanoid) on the static grid too (1) or on the work queue (0)
-#ifndef MG_COMPACT_STATIC32
-#define MG_COMPACT_STATIC32 0
-#endif
-// dynamic LDS added to every step-kernel launch (0; an occupancy A/B variant pads it to hold fewer waves per CU)
 // an explicit VGPR budget for k_env_step (0: the waves_per_eu budget); register-pressure experiments only
 #ifndef MG_NUM_VGPR
 #define MG_NUM_VGPR 0
@@ -34,17 +30,6 @@
 #define MG_VGPR_ATTR __attribute__((amdgpu_num_vgpr(MG_NUM_VGPR)))
 #else
 #define MG_VGPR_ATTR
-#endif
-#ifndef MG_LDS_PAD
-#define MG_LDS_PAD 0
-#endif
-// the locomotion observation head on four team lanes (mg::obs_head_team) instead of the leader (0: mg::obs_head)
-// the locomotion task layer's per-env scalars (progress, potentials) loaded at the start of the step (0: after it)
-#ifndef MG_TASK_PREFETCH
-#define MG_TASK_PREFETCH 1
-#endif
-#ifndef MG_TEAM_OBS_HEAD
-#define MG_TEAM_OBS_HEAD 1
 #endif
 
 namespace mgi {
@@ -101,10 +86,11 @@ struct Shape {
   static constexpr int kThreads = 64 * W;
   static constexpr int E = E1 * W;  // teams per block
   static_assert(per_cu(W) >= 1, "one block must fit the CU's LDS");
-  // one work item per wave on a static grid (no work queue): the one-wave blocks, and the compact instances'
+  // one work item per wave on a static grid (no work queue): the one-wave blocks, and the compact 16-lane instances'
   // two-wave blocks (a block's waves hold envs of like cost under the sort, so little of its LDS waits on a slower
-  // partner, and the queue's loop costs registers at the 168-VGPR budget)
-  static constexpr bool kStatic = W == 1 || (TL::kCompact && (T == 16 || MG_COMPACT_STATIC32));
+  // partner, and the queue's loop costs registers at the 168-VGPR budget); the compact 32-lane instances (Humanoid)
+  // stay on the work queue
+  static constexpr bool kStatic = W == 1 || (TL::kCompact && T == 16);
 };
 
 // ------------------------------------------------------------------------------------------------ work queue
@@ -131,17 +117,13 @@ __device__ __forceinline__ int wq_next(unsigned* wq, int grid_waves) {
 }
 // kernel span (mg_kernel_span_begin): lane 0 of each wave stores its start and end times (GPU wall clock) into the
 // wave's own pair of the launch's slot -- plain stores to distinct addresses, no atomics (a same-address atomic per
-// wave cost Ant 12 % in its first form); mg_kernel_span_read reduces them.  A kernel-argument branch otherwise.
-// (MG_NO_SPAN: compiled out, the A/B variant that checks the hooks cost the timed launches nothing)
+// wave cost Ant 12 % in its first form); mg_kernel_span_read reduces them.  A kernel-argument branch otherwise
+// (a build with the hooks compiled out ran no faster, profiles/r05/ab_span_hooks.txt).
 __device__ __forceinline__ void span_start(unsigned long long* clk, int wave) {
-#ifndef MG_NO_SPAN
   if (clk && (threadIdx.x & 63) == 0) clk[2 * (size_t)wave] = (unsigned long long)wall_clock64();
-#endif
 }
 __device__ __forceinline__ void span_end(unsigned long long* clk, int wave) {
-#ifndef MG_NO_SPAN
   if (clk && (threadIdx.x & 63) == 0) clk[2 * (size_t)wave + 1] = (unsigned long long)wall_clock64();
-#endif
 }
 // sort: block 0 zeroes the bin totals this launch's permutation was built from (k_oscatter, their last reader, has
 // finished: stream order), so every sort starts from zero and the launches hold no host-side parity (graph replays)
@@ -179,10 +161,7 @@ __global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, OBJ, DR, LAY>::kThreads))
   t.init(&lds[team].v, &tile, m, &p);
   if constexpr (DR) {  // domain randomization: this actor's env_props row into the team's DrTile
     mg::load_dr<T>(&drt[team], v.env_props + (size_t)v.env_props_stride * ac, m, t.tl);
-    t.drn = &drt[team].node[0][0];
-    t.drg = drt[team].geom;
-    t.drt = &drt[team].ten[0][0];
-    t.dro = drt[team].obj;
+    t.bind_dr(&drt[team]);
   }
   if (OBJ && t.tl < 4) {  // applied force on the object row of rb_forces (apply_rigid_body_force_tensors)
     const float* fr = v.rb_forces ? v.rb_forces + ((size_t)(m->num_bodies + 2) * ac + m->num_bodies) * 3 : nullptr;
@@ -297,17 +276,14 @@ __device__ __forceinline__ void env_step_item(
   t.init(&L, &tile, m, &p, SH::W > 1);
   if constexpr (DR) {  // domain randomization: this actor's env_props row into the team's DrTile
     mg::load_dr<T>(&drt[team], v.env_props + (size_t)v.env_props_stride * ac, m, t.tl);
-    t.drn = &drt[team].node[0][0];
-    t.drg = drt[team].geom;
-    t.drt = &drt[team].ten[0][0];
-    t.dro = drt[team].obj;
+    t.bind_dr(&drt[team]);
   }
   mg::wsync();
   const int64_t reset_in = tb.reset[ac];
   // the task layer's per-env scalars, loaded now so that their latency hides under the physics (nothing in the
   // step writes them before the task layer does); not for the compact 16-lane kernel, whose 168 registers it costs
   // (profiles/r06/ab_task_prefetch.txt: Ant 65,536 -0.3 %, MA-Ant -0.4 %; Humanoid +0.6 %, Ant 8,192 +0.9 %)
-  constexpr bool kTaskPf = MG_TASK_PREFETCH && !(SH::TL::kCompact && T == 16);
+  constexpr bool kTaskPf = !(SH::TL::kCompact && T == 16);
   int64_t progress_in = 0;
   float pot_in = 0.0f, prev_in = 0.0f;
   if constexpr (kTaskPf) {
@@ -397,11 +373,7 @@ __device__ __forceinline__ void env_step_item(
   if (tp.task_id == MG_TASK_CARTPOLE) {
     if (t.tl < 4) ost[t.tl] = L.st().dof[t.tl];
   } else {
-#if MG_TEAM_OBS_HEAD
     mg::obs_head_team(&tp, off, L.st().root, t.tl, t.tb, &pot, &prev, up, hd, ost);  // lanes 0..3, T >= 16
-#else
-    if (t.tl == 0) mg::obs_head(&tp, off, L.st().root, &pot, &prev, up, hd, ost);
-#endif
     const bool hum = tp.task_id == MG_TASK_HUMANOID;
     for (int q = t.tl; q < nd; q += T) {
       ost[12 + q] = mg::t_unscale(L.st().dof[2 * q], tp.dof_lower[q], tp.dof_upper[q]);
@@ -574,10 +546,7 @@ __device__ __forceinline__ void hand_step_item(
   t.init(&L, &tile, m, &p, SH::W > 1);
   if constexpr (DR) {  // domain randomization: this actor's env_props row into the team's DrTile
     mg::load_dr<T>(&drt[team], v.env_props + (size_t)v.env_props_stride * ec, m, t.tl);
-    t.drn = &drt[team].node[0][0];
-    t.drg = drt[team].geom;
-    t.drt = &drt[team].ten[0][0];
-    t.dro = drt[team].obj;
+    t.bind_dr(&drt[team]);
   }
   t.ph_start();
   const uint64_t gid = (uint64_t)(tb.env_offset + ec);
@@ -853,14 +822,14 @@ static int launch_wq(K kern, hipStream_t s, const mg_sim* sim, bool ordered, A..
     if (c.k == kp && c.dev == sim->device) resident = c.blocks;
   if (resident <= 0) {
     int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, SH::kThreads, MG_LDS_PAD + sim->lds_pad) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, SH::kThreads, sim->lds_pad) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, sim->device) != hipSuccess || per_cu <= 0 ||
         cus <= 0)
       return fail(MG_EDEVICE, "mg_env_step: occupancy query failed");
     resident = per_cu * cus;
     if (getenv("MIGYM_PRINT_OCC"))  // diagnostics: the resident blocks the runtime reports for this kernel
       fprintf(stderr, "migym: step kernel W=%d: %d blocks per CU (%d waves), lds pad %d\n", SH::W, per_cu,
-              per_cu * SH::W, MG_LDS_PAD + sim->lds_pad);
+              per_cu * SH::W, sim->lds_pad);
     for (Entry& c : cache)
       if (!c.k) { c = Entry{kp, sim->device, resident}; break; }
   }
@@ -889,7 +858,7 @@ static int launch_wq(K kern, hipStream_t s, const mg_sim* sim, bool ordered, A..
     ord.done = sim->d_bq + 2 * kOrderBuckets;
   }
   // one-wave blocks: the static grid, one block per item; multi-wave blocks: the resident capacity (work queue)
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(SH::kThreads), MG_LDS_PAD + sim->lds_pad, s, args..., sim->d_wq, ord);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(SH::kThreads), sim->lds_pad, s, args..., sim->d_wq, ord);
   return MG_OK;
 }
 

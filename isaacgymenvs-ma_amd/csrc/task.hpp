@@ -221,37 +221,12 @@ __device__ void reset_env(const mg_task_params* tp, const float* off, const floa
   reset_root(tp, off, root, pot, prev_pot);
 }
 
-// the first 12 observation values of compute_{ant,humanoid}_observations (ant.py:401-406,
-// humanoid.py:401-413) + the potentials / basis vectors
-__device__ __forceinline__ void obs_head(const mg_task_params* tp, const float* off, const float* root, float* pot,
-                                         float* prev_pot, float* up, float* heading, float* o) {
-  LocoFeat f;
-  loco_features(tp, root, off, f);
-  *prev_pot = *pot;
-  *pot = f.potential;
-  for (int i = 0; i < 3; i++) { up[i] = f.up_vec[i]; heading[i] = f.heading_vec[i]; }
-  int k = 0;
-  o[k++] = root[2];
-  for (int i = 0; i < 3; i++) o[k++] = f.vel_loc[i];
-  if (tp->task_id == MG_TASK_ANT) {
-    for (int i = 0; i < 3; i++) o[k++] = f.angvel_loc[i];
-    o[k++] = f.yaw;
-    o[k++] = f.roll;
-    o[k++] = f.angle_to_target;
-  } else {
-    for (int i = 0; i < 3; i++) o[k++] = f.angvel_loc[i] * tp->angular_velocity_scale;
-    o[k++] = t_normalize_angle(f.yaw);
-    o[k++] = t_normalize_angle(f.roll);
-    o[k++] = t_normalize_angle(f.angle_to_target);
-  }
-  o[k++] = f.up_proj;
-  o[k++] = f.heading_proj;
-}
-
-// obs_head on a team's first four lanes instead of its leader alone: the same operations on the same operands
-// (FMA contraction is off here, so every value is bit-identical to obs_head's), with the per-env serial chain of
-// four vector rotations, three atan2 and (Humanoid) three angle normalisations issued once per wave instead of
-// one after another.  Lane k of the team: k = 0 rotates e_z (up_vec) and takes the roll, k = 1 rotates e_x
+// the first 12 observation values of compute_{ant,humanoid}_observations (ant.py:401-406, humanoid.py:401-413) + the
+// potentials / basis vectors -- the head of obs_env above (loco_features) -- on a team's first four lanes instead of
+// its leader alone: the same operations on the same operands (FMA contraction is off here, so every value is
+// bit-identical to obs_env's), with the per-env serial chain of four vector rotations, three atan2 and (Humanoid)
+// three angle normalisations issued once per wave instead of one after another (round 5, against the
+// leader alone: Humanoid 32,768 +0.6 / +0.9 %, Ant 65,536 +0.1 / +0.5 %, profiles/r05/ab_team_obs_head.txt).  Lane k of the team: k = 0 rotates e_z (up_vec) and takes the roll, k = 1 rotates e_x
 // (heading_vec) and takes the yaw, k = 2 rotates the velocity into the torso frame and takes the walk-target angle
 // (then angle_to_target = target angle - yaw), k = 3 rotates the angular velocity; the leader gathers the results
 // by shuffles and writes the 12 head entries.  All lanes of the team call it (T >= 4); pot / prev / up / heading

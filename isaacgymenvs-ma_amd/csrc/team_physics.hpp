@@ -43,57 +43,7 @@ namespace mg {
 // reference arithmetic in task.hpp / hand_task.hpp keeps contraction off).  The caller's FP state is
 // restored at the end of this header.
 #pragma float_control(push)
-#ifndef MG_PHYS_CONTRACT
-#define MG_PHYS_CONTRACT 1  // 0: no FMA contraction in the physics (a parity A/B only)
-#endif
-#if MG_PHYS_CONTRACT
 #pragma clang fp contract(fast)
-#else
-#pragma clang fp contract(off)
-#endif
-// per-phase contraction switches (parity A/B: which phase's FMA contraction moves the results off the fp64 oracle;
-// MG_NOCONTRACT_MASK bits: 1 PGS visit, 2 ABA, 4 test solves, 8 FK, 16 integrate + velocity cap, 32 row Jacobians)
-#ifndef MG_NOCONTRACT_MASK
-#define MG_NOCONTRACT_MASK 0
-#endif
-#define MG_NC_OFF _Pragma("clang fp contract(off)")
-// PGS visit products kept out of FMAs: 1 the velocity update nu += Y dl (the default, round 6), 2 the impulse update.
-// Fusing the velocity update moved the DOF velocities off the fp64 oracle: the fraction of them within north_star's
-// 1e-4 relative fell 0.8 % below the oracle's own fp32 build (Ant 16,384 / 65,536, MA-Ant), against 0.25 % unfused
-// (the per-phase A/B: only this product matters; profiles/r06/ab_pgs_fusion.txt); it costs Ant 65,536 1.3 %
-#ifndef MG_PGS_UNFUSE
-#define MG_PGS_UNFUSE 1
-#endif
-#if MG_NOCONTRACT_MASK & 1
-#define MG_NC_PGS MG_NC_OFF
-#else
-#define MG_NC_PGS
-#endif
-#if MG_NOCONTRACT_MASK & 2
-#define MG_NC_ABA MG_NC_OFF
-#else
-#define MG_NC_ABA
-#endif
-#if MG_NOCONTRACT_MASK & 4
-#define MG_NC_TS MG_NC_OFF
-#else
-#define MG_NC_TS
-#endif
-#if MG_NOCONTRACT_MASK & 8
-#define MG_NC_FK MG_NC_OFF
-#else
-#define MG_NC_FK
-#endif
-#if MG_NOCONTRACT_MASK & 16
-#define MG_NC_INT MG_NC_OFF
-#else
-#define MG_NC_INT
-#endif
-#if MG_NOCONTRACT_MASK & 32
-#define MG_NC_JAC MG_NC_OFF
-#else
-#define MG_NC_JAC
-#endif
 
 // Block-shared LDS copy of the model tables the hot loops read ("model tile"):
 // every per-node / per-geom constant is an LDS read (~64 cycles) instead of a dependent global load.
@@ -289,9 +239,6 @@ __device__ __forceinline__ void tangent_basis_t(V3 n, V3* t1, V3* t2) {
   *t2 = cross(n, t);
 }
 
-#ifndef MG_PART_B_LDS
-#define MG_PART_B_LDS 0  // part-B PGS rows in the dead tree tiles (TeamLDS::PBL); an A/B variant
-#endif
 template <int T, int MN, int MC, int OBJ = 0>
 struct TeamLDS {
   // row capacity, rounded up to a multiple of the PGS prefetch depth (the sweep pads to it)
@@ -301,27 +248,12 @@ struct TeamLDS {
   // (not for the egg instance: 17.16 vs 17.73 M env-steps/s and 450 vs 409 MB per launch, measured on its fp32 build)
   static constexpr int KR0 = OBJ == MG_GT_ELLIPSOID ? MG_KJY_EGG : (OBJ ? MG_KJY_HAND : (T >= 32 ? MG_KJY_LOCO32 : kJYRegs));
   static constexpr int KR = (KR0 < MR ? KR0 : MR) / kPgsPrefetch * kPgsPrefetch;  // right-hand sides per test solve (rows of 2-4 contacts)
-  // part-B rows whose (J, Y) columns live in the LDS left dead by the tree phases (R[1..MN-1], x, V: written by
-  // fk(), read by collide(), not again until the next fk()) instead of scratch, one float per lane and row for J
-  // and for Y; locomotion instances only (the hand kernels keep their tree tiles live longer: egg_stage /
-  // reload_tree, the object rows).  Off by default (MG_PART_B_LDS=1 builds it): same box, it cut Humanoid 32,768's
-  // HBM-side traffic 156 -> 119 MB per launch and Ant 65,536's 70.5 -> 61.6 MB, but cost 1.2 % (Humanoid) to 3 %
-  // (Ant 16,384, MA-Ant) of throughput (profiles/r05/ab_part_b_lds.txt)
-  static constexpr int PBL0 = (OBJ || !MG_PART_B_LDS) ? 0 : (int)(((MN - 1) * 9 + MN * 9) / (2 * T));
-  static constexpr int PBL = KR + PBL0 <= MR ? PBL0 : (MR - KR > 0 ? MR - KR : 0);
-#if MG_PART_B_LDS
-  // S first: the link axes outlive the solve (clamp_ang_vel reads them after the PGS), as does R[0]; the storage
-  // from R[1] through V is dead from the end of collide() to the next fk(), and holds part-B PGS rows (PBL)
-  float S[MN][6];
-  float R[MN][9];
-  float x[MN][3];
-  float V[MN][6];
-#else
+  // (the rows past KR stay in scratch: keeping them in the LDS the tree phases leave dead between collide() and the
+  // next fk() cut the HBM-side traffic but cost 1.2 % to 3 % of throughput, profiles/r05/ab_part_b_lds.txt)
   float R[MN][9];
   float x[MN][3];
   float V[MN][6];
   float S[MN][6];
-#endif
   float U[MN][6];
   float Dinv[MN];
   float L0[21];
@@ -420,7 +352,7 @@ struct TeamLDS {
   }
 };
 
-// The compact team layout of the 16- and 32-lane locomotion instances (Ant, MA-Ant, Humanoid; MG_COMPACT_LDS,
+// The compact team layout of the 16- and 32-lane locomotion instances (Ant, MA-Ant, Humanoid;
 // common.hpp mg_compact_layout): Ant 4.2 -> 2.8 KB per team, Humanoid 9.0 -> 5.6 KB, so that twelve waves fit a CU's
 // 160 KB (three per SIMD) instead of eight.  What it changes against TeamLDS:
 //   * region A holds the poses R, x, V from fk() to collide()'s geom staging, then the constraint rows (build_rows()
@@ -457,7 +389,6 @@ struct TeamLDSC {
   static constexpr int RB = T >= 32 ? MG_RB_LOCO32C : (kRBLoco <= T ? kRBLoco : 6);
   static constexpr int KR0 = T >= 32 ? MG_KJY_LOCO32C : kJYRegs;
   static constexpr int KR = (KR0 < MR ? KR0 : MR) / kPgsPrefetch * kPgsPrefetch;
-  static constexpr int PBL = 0;
   static constexpr int OROWS = 1;
   static constexpr int HX = 0;
   static constexpr bool kCompact = true;
@@ -928,17 +859,8 @@ struct Team {
   using L = TeamLDSOf<T, MN, MC, OBJ, MG, MP, LAY>;
   using MT = ModelTile<MN, MG, MP, tile_hull_verts(OBJ)>;
   static constexpr int MR = L::MR;
-#ifndef MG_HW_TRIG_T16
-#define MG_HW_TRIG_T16 1
-#endif
-#ifndef MG_SENSOR_MASKS
-#define MG_SENSOR_MASKS 1  // outputs(): per-sensor contact masks by ballots instead of every sensor scanning every contact
-#endif
-#ifndef MG_LOAD_RSQ
-#define MG_LOAD_RSQ 1  // load(): free-base root quaternions normalised by rsq
-#endif
-  // the hardware sine / cosine for the 16-lane teams (Ant, MA-Ant), the library's elsewhere (device_math.hpp psincos)
-  static constexpr bool kHwTrig = MG_HW_TRIG_T16 && T == 16 && OBJ == 0;
+  // the hardware sine / cosine for the 16-lane teams (Ant, MA-Ant), poly_sincos elsewhere (device_math.hpp psincos)
+  static constexpr bool kHwTrig = T == 16 && OBJ == 0;
   L* s;
   const MT* mt;
   const mg_model* m;
@@ -992,6 +914,12 @@ struct Team {
   const float* drg;    // geom friction
   const float* drt;    // tendons (stride 2)
   const float* dro;    // object [mass, friction, scale]
+  __device__ __forceinline__ void bind_dr(const DrTile<MN, MG>* d) {
+    drn = &d->node[0][0];
+    drg = d->geom;
+    drt = &d->ten[0][0];
+    dro = d->obj;
+  }
   // node property row [mass, armature, damping, stiffness, lower, upper, drive kp, effort, frictionloss]: the DR row
   // or the tile's nf[24..32]
   __device__ __forceinline__ const float* nprop(int i) const { return drn ? drn + MG_EP_NODE_WIDTH * i : &mt->nf[i][24]; }
@@ -1066,7 +994,6 @@ struct Team {
   // by the same operations either way)
   template <bool POSE = false>
   __device__ __forceinline__ void fk() {
-    MG_NC_FK
     if (OBJ) oR = quat_to_mat(oq[0], oq[1], oq[2], oq[3]);
     const M3 Rr = quat_to_mat(q0[0], q0[1], q0[2], q0[3]);
     if (tl == 0) {
@@ -1149,7 +1076,6 @@ struct Team {
 
   // ---------------------------------------------------------------- ABA (unconstrained step)
   __device__ __forceinline__ void aba() {
-    MG_NC_ABA
     if (node >= 0) {
       const V3 o = ld3(s->x[0]);
       const float* nf = mt->nf[node];
@@ -1203,11 +1129,7 @@ struct Team {
       tj = tau + tadd + ttend - bb * nu - kk * (qj - ref + h * nu);
       // dry joint friction (MJCF frictionloss; domain randomization of dof_properties.friction scales this torque
       // bound, column 8 of the DR node row -- not a PhysX-style friction coefficient): -f tanh(qd / v_s), linearly implicit
-#ifndef MG_NO_FRICTIONLOSS  // (A/B builds only)
       const float fl = np[8];  // nf[32] or the DR row's
-#else
-      const float fl = 0.0f;
-#endif
       if (fl > 0.0f) {
         const float th = ptanh(nu * (1.0f / MG_FRICTIONLOSS_VS));
         tj -= fl * th;
@@ -1369,7 +1291,6 @@ struct Team {
   // level by level, each lane gathers its ancestor's y values with one bpermute per column (no LDS
   // round trip or barrier per level).  y[q] = this lane's entry of Y_{r0+q} (0 off the columns).
   __device__ __forceinline__ void test_solve(int r0, int nrows_, const float* Wv, float* y) {
-    MG_NC_TS
     for (int i = tl; i < L::RB * MN; i += T) s->ut(0)[i] = 0.0f;
     wsync();
     if (tl < L::RB) {
@@ -1577,7 +1498,6 @@ struct Team {
   // g = Sl_ang x (p - o) + Sl_lin, so J_r = sign (d_r . g) (= sign Sl . [(p - o) x d_r; d_r]).
   // Limit rows: +-1 on the DOF's lane.  Object lanes: the stored object part of the contact rows.
   __device__ __forceinline__ void batch_jacobians(int r0, int nrows_, float* J) const {
-    MG_NC_JAC
 #pragma unroll
     for (int q = 0; q < 3; q++) J[q] = 0.0f;
     if (OBJ && objl) {
@@ -2650,32 +2570,6 @@ struct Team {
     // (J_r[j], Y_r[j]) of the first KR rows live in registers (the index is wave-uniform, so the compiler
     // promotes the arrays to VGPRs and addresses them with relative moves); the remaining rows are
     // private arrays in scratch.  Wave-uniform branches pick the side.
-#if MG_PART_B_LDS
-    constexpr int KR = L::KR, PBL = L::PBL;
-    float Jr[KR > 0 ? KR : 1], Yr[KR > 0 ? KR : 1];
-    float Js[MR - KR - PBL > 0 ? MR - KR - PBL : 1], Ys[MR - KR - PBL > 0 ? MR - KR - PBL : 1];
-    // part B: rows KR .. KR + PBL - 1 in the dead tree tiles (J rows, then Y rows, lane-contiguous), the rest scratch
-    float* const pbj = &s->R[1][0] + tl;
-    float* const pby = pbj + PBL * T;
-#define MG_JSET(r, j, y)                                   \
-  do {                                                     \
-    if ((r) < KR) {                                        \
-      Jr[r] = (j); Yr[r] = (y);                            \
-    } else if ((r) < KR + PBL) {                           \
-      pbj[((r) - KR) * T] = (j); pby[((r) - KR) * T] = (y); \
-    } else {                                               \
-      Js[(r) - KR - PBL] = (j); Ys[(r) - KR - PBL] = (y);   \
-    }                                                      \
-  } while (0)
-#define MG_JGET(r, jo, yo)                                     \
-  do {                                                         \
-    if ((r) < KR + PBL) {                                      \
-      jo = pbj[((r) - KR) * T]; yo = pby[((r) - KR) * T];      \
-    } else {                                                   \
-      jo = Js[(r) - KR - PBL]; yo = Ys[(r) - KR - PBL];        \
-    }                                                          \
-  } while (0)
-#else
     constexpr int KR = L::KR;
     float Jr[KR > 0 ? KR : 1], Yr[KR > 0 ? KR : 1];
     float Js[MR - KR > 0 ? MR - KR : 1], Ys[MR - KR > 0 ? MR - KR : 1];
@@ -2691,7 +2585,6 @@ struct Team {
   do {                                   \
     jo = Js[(r) - KR]; yo = Ys[(r) - KR]; \
   } while (0)
-#endif
     for (int r0 = 0; r0 < wave_rows; r0 += L::RB) {
       float jb[L::RB], yb[L::RB];
 #pragma unroll
@@ -2766,7 +2659,6 @@ struct Team {
     float tisp = ihs, tbz = TGS ? p->baumgarte : 0.0f;
     const int n_sweeps = TGS ? p->pos_iters + max(p->pos_iters, p->vel_iters) : p->pos_iters;
     auto visit = [&](float J, float Y, const typename L::Row& R, int r) {
-      MG_NC_PGS
       const float v = team_sum<T>(J * nu, tb);
       const float lam = R.lam, m = R.mu;
       // friction rows (m = mu >= 0): [-mu lambda_n, mu lambda_n]; normal / limit rows (m < 0):
@@ -2780,22 +2672,17 @@ struct Team {
         const float te = e >= 0.0f ? -e * tisp : fminf(-tbz * e * ihs, p->max_depen_vel);
         tgt = fric ? 0.0f : te;
       }
-#if MG_PGS_UNFUSE & 2
-      float dlr = (tgt - v) * R.iw;
-      asm volatile("" : "+v"(dlr));  // (A/B: the impulse update's product rounded, not fused)
-      const float lnew = __builtin_amdgcn_fmed3f(lam + dlr, -t, hi);
-#else
       const float lnew = __builtin_amdgcn_fmed3f(lam + (tgt - v) * R.iw, -t, hi);
-#endif
       lamn = m == -1.0f ? lnew : lamn;
       s->rows()[r].lam = lnew;
-#if MG_PGS_UNFUSE & 1
+      // the velocity update nu += Y dl with its product rounded, not fused into the add (the barrier keeps it out of
+      // an FMA; the impulse update above is left to fuse).  Fused, it moved the DOF velocities off the fp64 oracle:
+      // the fraction of them within north_star's 1e-4 relative fell 0.8 % below the oracle's own fp32 build (Ant
+      // 16,384 / 65,536, MA-Ant), against 0.25 % unfused (per phase, only this product matters;
+      // profiles/r06/ab_pgs_fusion.txt); it costs Ant 65,536 1.3 %
       float dv = Y * (lnew - lam);
-      asm volatile("" : "+v"(dv));  // (A/B: the velocity update's product rounded, not fused)
+      asm volatile("" : "+v"(dv));
       nu += dv;
-#else
-      nu += Y * (lnew - lam);
-#endif
     };
     const int pa = prow < KR ? prow : KR;  // rows of part A
     float pJ[PF], pY[PF];
@@ -2891,7 +2778,6 @@ struct Team {
   // which holds t = 0 because the parent is clamped already; slides carry the parent's w.  Same rule as the
   // oracle's clamp_ang_vel.  A team bound |w_root| + sum |qd| <= W (no link can reach the cap) skips the pass.
   __device__ __forceinline__ void clamp_ang_vel() {
-    MG_NC_INT
     const float W = m->link_max_ang_vel;
     if (W > 0.0f) {
       const V3 w0 = freeb ? v3(__shfl(nu, tb), __shfl(nu, tb + 1), __shfl(nu, tb + 2)) : v3(0, 0, 0);
@@ -2947,7 +2833,6 @@ struct Team {
   }
 
   __device__ __forceinline__ void integrate() {
-    MG_NC_INT
     // root pose (lane 0 gathers the twist from lanes 0..5)
     float w0 = __shfl(nu, tb + 0), w1 = __shfl(nu, tb + 1), w2 = __shfl(nu, tb + 2);
     float v0 = __shfl(nu, tb + 3), v1 = __shfl(nu, tb + 4), v2 = __shfl(nu, tb + 5);
@@ -3174,7 +3059,6 @@ struct Team {
     if constexpr (T >= 32 && !OBJ) {
       if (sens_out && NS > 0) sensors_by_team_sums(sens_out, NS);
     } else if (sens_out && NS > 0) {
-#if MG_SENSOR_MASKS
       // which sensors' bodies each contact touches, one lane per contact (chunks of T lanes), as per-sensor bit masks
       // by ballots: sensor lane j then visits only its own contacts (a foot has one or two) instead of scanning all
       // of them with two dependent LDS lookups each; same contacts, same increasing order, so the same sums bit for bit
@@ -3195,40 +3079,31 @@ struct Team {
           if (tl == j) own |= bits << c0;
         }
       }
-#endif
       if (tl < NS) {
-      const int body = m->sensor_body[tl], nd = m->body_node[body];
-      M3 Rn;
-      for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) Rn.m[a][b] = s->R[nd][3 * a + b];
-      M3 Rb = mul(Rn, quat_to_mat(m->body_quat[body][0], m->body_quat[body][1], m->body_quat[body][2],
-                                  m->body_quat[body][3]));
-      V3 xb = ld3(s->x[nd]) + mul(Rn, ld3(m->body_pos[body]));
-      V3 F = v3(0, 0, 0), Tq = v3(0, 0, 0);
-#if MG_SENSOR_MASKS
-      for (unsigned long long mm = own; mm; mm &= mm - 1ull) {
-        const int c = __builtin_ctzll(mm);
-        const float sg = (cside(c, 2) >= 0 && mt->gbody[cside(c, 2)] == body) ? 1.0f : -1.0f;
-#else
-      for (int c = 0; c < s->ncon; c++) {
-        float sg = 0.0f;
-        if (cside(c, 2) >= 0 && mt->gbody[cside(c, 2)] == body) sg = 1.0f;
-        else if (cside(c, 3) >= 0 && mt->gbody[cside(c, 3)] == body) sg = -1.0f;
-        if (sg == 0.0f) continue;
-#endif
-        V3 f;
-        if constexpr (L::kCompact) {
-          f = ld3(s->fc(c)) * (sg * ih);
-        } else {
-          const V3 n = ld3(s->cn[c]), t1 = ld3(s->ct1[c]), t2 = ld3(s->ct2[c]);  // build_rows' basis
-          f = (n * s->rows()[3 * c].lam + t1 * s->rows()[3 * c + 1].lam + t2 * s->rows()[3 * c + 2].lam) * (sg * ih);
+        const int body = m->sensor_body[tl], nd = m->body_node[body];
+        M3 Rn;
+        for (int a = 0; a < 3; a++)
+          for (int b = 0; b < 3; b++) Rn.m[a][b] = s->R[nd][3 * a + b];
+        M3 Rb = mul(Rn, quat_to_mat(m->body_quat[body][0], m->body_quat[body][1], m->body_quat[body][2],
+                                    m->body_quat[body][3]));
+        V3 xb = ld3(s->x[nd]) + mul(Rn, ld3(m->body_pos[body]));
+        V3 F = v3(0, 0, 0), Tq = v3(0, 0, 0);
+        for (unsigned long long mm = own; mm; mm &= mm - 1ull) {
+          const int c = __builtin_ctzll(mm);
+          const float sg = (cside(c, 2) >= 0 && mt->gbody[cside(c, 2)] == body) ? 1.0f : -1.0f;
+          V3 f;
+          if constexpr (L::kCompact) {
+            f = ld3(s->fc(c)) * (sg * ih);
+          } else {
+            const V3 n = ld3(s->cn[c]), t1 = ld3(s->ct1[c]), t2 = ld3(s->ct2[c]);  // build_rows' basis
+            f = (n * s->rows()[3 * c].lam + t1 * s->rows()[3 * c + 1].lam + t2 * s->rows()[3 * c + 2].lam) * (sg * ih);
+          }
+          F = F + f;
+          Tq = Tq + cross(ld3(s->cp[c]) - xb, f);
         }
-        F = F + f;
-        Tq = Tq + cross(ld3(s->cp[c]) - xb, f);
-      }
-      V3 Fl = mulT(Rb, F), Tl = mulT(Rb, Tq);
-      float* o = sens_out + 6 * tl;
-      o[0] = Fl.x; o[1] = Fl.y; o[2] = Fl.z; o[3] = Tl.x; o[4] = Tl.y; o[5] = Tl.z;
+        V3 Fl = mulT(Rb, F), Tl = mulT(Rb, Tq);
+        float* o = sens_out + 6 * tl;
+        o[0] = Fl.x; o[1] = Fl.y; o[2] = Fl.z; o[3] = Tl.x; o[4] = Tl.y; o[5] = Tl.z;
       }
     }
     if (dforce_out && node > 0) {
@@ -3240,11 +3115,7 @@ struct Team {
       } else {
         t += -np[2] * nu - np[3] * qj;
       }
-#ifndef MG_NO_FRICTIONLOSS
       const float fl = np[8];
-#else
-      const float fl = 0.0f;
-#endif
       if (fl > 0.0f) t -= fl * ptanh(nu * (1.0f / MG_FRICTIONLOSS_VS));  // the joint friction at the post-step state
       // the node's own limit rows of the last substep (lower, then upper: consecutive from the index build_rows
       // kept in sat), instead of a scan over every limit row
@@ -3267,7 +3138,7 @@ struct Team {
     // quaternion itself (the same operations on every lane: no shuffles from the leader)
     {
       p0 = ld3(root);
-      if (MG_LOAD_RSQ && freeb) {
+      if (freeb) {
         // free-base roots: a 1-ulp reciprocal square root instead of a correctly rounded root and four divisions
         // (~60 instructions; the fixed-base hand and Cartpole keep the exact form, their parity cases being tighter)
         const float in = prsq(root[3] * root[3] + root[4] * root[4] + root[5] * root[5] + root[6] * root[6]);

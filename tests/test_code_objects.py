@@ -43,3 +43,31 @@ def test_checker_sees_a_real_call(tmp_path):
         pytest.skip("hipcc unavailable: " + r.stderr[-200:])
     found = codeobj.calls(str(so))
     assert any("s_swappc_b64" == i for _, _, i in found) and any("_Z1ff" in f for _, f, _ in found), found
+
+
+@pytest.mark.skipif(not codeobj.have_objdump(), reason="llvm-objdump not installed")
+def test_diff_ignores_comments_and_names_a_changed_kernel(tmp_path):
+    """the comparison itself (codeobj.diff): sources that differ in comments and blank lines only build the same
+    code objects; one changed arithmetic constant is reported, under the kernel that holds it"""
+    import subprocess
+    body = ("#include <hip/hip_runtime.h>\n"
+            "__global__ void k_keep(float* p) { p[threadIdx.x] += 1.0f; }\n"
+            "%s__global__ void k_scale(float* p) { p[threadIdx.x] = p[threadIdx.x] * %s + 0.5f; }\n")
+    sos = {}
+    for name, text in (("a", body % ("", "3.0f")),
+                       ("b", body % ("\n// a comment, and blank lines\n\n", "3.0f /* the factor */")),
+                       ("c", body % ("", "3.25f"))):
+        d = tmp_path / name   # (the same file name in each: the source's name is part of the code object's notes)
+        d.mkdir()
+        (d / "k.hip").write_text(text)
+        sos[name] = str(d / "libk.so")
+        r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-o", sos[name],
+                            str(d / "k.hip")], capture_output=True, text=True)
+        if r.returncode != 0:
+            pytest.skip("hipcc unavailable: " + r.stderr[-200:])
+    assert codeobj.diff(sos["a"], sos["b"]) == (1, [])
+    n, changed = codeobj.diff(sos["a"], sos["c"])
+    assert n == 1 and len(changed) == 1, changed
+    k, secs, fns = changed[0]
+    assert k == 0 and ".text" in secs, changed
+    assert len(fns) == 1 and "k_scale" in fns[0], fns   # and not k_keep, which is the same code

@@ -4,7 +4,7 @@
 replaced by the trace's post-simulate state (what the traces' fake ``gym.simulate`` wrote,
 tests/golden/make_traces.py).  Everything else in the launch is the bench path's code: the action
 clamp and actuation / PD targets, the masked reset_idx with the reference's injected draws, the
-team-parallel observation staging (``obs_head``, LDS staging, hand ``obs_map``), the team-summed
+team-parallel observation staging (``obs_head_team``, LDS staging, hand ``obs_map``), the team-summed
 reward terms (``reward_from_sums``), ``compute_hand_reward`` and its running mean, timeouts, the obs
 clamp and the write-back.
 
@@ -100,7 +100,7 @@ def loco_setup(task):
 
 @pytest.mark.parametrize("task", ["Ant", "Humanoid"])
 def test_fused_env_step_replays_reference_trace(lib, task):
-    """k_env_step's own task layer (obs_head, LDS-staged DOF/sensor/action columns, team-summed reward
+    """k_env_step's own task layer (obs_head_team, LDS-staged DOF/sensor/action columns, team-summed reward
     terms, masked reset) replays trace_{ant,humanoid}.npz: ant.py:287-297, 325-408; humanoid.py:287-413."""
     d = load(f"trace_{task.lower()}.npz")
     spec, sp, tp = loco_setup(task)

@@ -480,7 +480,7 @@ def assert_north_star_rtol(res, twin_factor=4.0, frac_margin=0.005):
             bad[g] = dict(v, allowed=a)
         # and element by element: the fraction of the group's entries within 1e-4 |x| alone, with no
         # floor, at least the fp32 twin's own fraction minus 0.5 % (measured round 6: Ant DOF velocities 88.9 % vs
-        # 89.1 %; the fused PGS velocity update had left them 0.8 % below, team_physics.hpp MG_PGS_UNFUSE)
+        # 89.1 %; the fused PGS velocity update had left them 0.8 % below, team_physics.hpp substep() visit)
         if v["frac_within_rtol"] < twin[g]["frac_within_rtol"] - frac_margin:
             bad[g + " (fraction within 1e-4 |x|)"] = {"gpu": v["frac_within_rtol"], "twin": twin[g]["frac_within_rtol"]}
     assert not bad, f"column groups outside 1e-4 |x| + a_g: {bad}"

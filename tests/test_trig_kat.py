@@ -1,5 +1,5 @@
-"""Known-answer test of the polynomial sine / cosine (device_math.hpp ``poly_sincos``, the MG_POLY_TRIG A/B option)
-on the host, over the inputs the VERDICT r5 fault review names: NaN, +-Inf, +-1e30, denormals, and the angles a
+"""Known-answer test of the polynomial sine / cosine (device_math.hpp ``poly_sincos``, the physics' pair outside the
+16-lane instances) on the host, over the inputs the VERDICT r5 fault review names: NaN, +-Inf, +-1e30, denormals, and the angles a
 Cartpole rollout actually visits ("the physics' sine / cosine").
 
 Both forms are checked: the float-quadrant form (quadrant = k - 4 floor(k / 4) in floating point, picked by float
