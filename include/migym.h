@@ -445,6 +445,13 @@ size_t mg_dr_noise_args_sizeof(void);
 int mg_debug_phase_cycles(uint64_t* out, int32_t reset);
 /* ... and the per-item rows behind it (an item = one wave's teams; cap items of MG_NUM_PHASES counts each) */
 int mg_debug_phase_waves(uint64_t* out, int32_t cap);
+/* test aid: the contact list of the first substep mg_sim_simulate would run from the bound state views, built by the
+ * step kernel's own collide path (the instance and layout the dispatcher picks for mg_sim_simulate; non-DR, PGS).
+ * count[a] = actor a's contacts; out[(a * cap + c) * 11 ..] = (nodeA, geomA, nodeB, geomB, point[3], normal[3],
+ * gap) of its contact c, ids -1 = ground, -2 = the free object.  out: num_actors * cap * 11 floats, count:
+ * num_actors ints (device memory).  cap below min(max_contacts, the instance's capacity) is MG_EINVAL.  Writes no
+ * state. */
+int mg_debug_contacts(mg_sim* sim, float* out, int32_t* count, int32_t cap, void* stream);
 
 int mg_sim_create(const mg_model* model, const mg_sim_params* params, int32_t num_envs, int32_t device,
                   mg_sim** out);

@@ -3,6 +3,7 @@
     hipcc -O3 --offload-arch=gfx950 -c csrc/migym.hip            (C ABI + the one-lane-per-env kernels)
     hipcc -O3 --offload-arch=gfx950 -c csrc/inst.hip -DMG_INST=i  (team kernels, one capacity instance
                                                                     per object, i < MG_NUM_INST)
+    hipcc ... -c csrc/inst.hip -DMG_INST=i -DMG_CONTACTS_TU       (the instance's contact read-out, tests only)
     hipcc -shared *.o -> migym/_lib/libmigym.so
 
 The objects compile in parallel (one process per translation unit, at most MIGYM_JOBS / os.cpu_count()).
@@ -78,9 +79,14 @@ def build(force=False, verbose=False, timing=False, variant=None, defines=(), ex
     objdir = os.path.join(HERE, "build", ("var_" + variant) if variant else ("timing" if timing else "release"))
     os.makedirs(objdir, exist_ok=True)
     objs, cmds = [], []
-    for i in range(-1, num_instances()):
-        o = os.path.join(objdir, "migym.o" if i < 0 else f"inst{i}.o")
-        src = SRC if i < 0 else INST
+    ninst = num_instances()
+    # -1: migym.hip; 0 .. ninst - 1: the instances; ninst .. 2 ninst - 1: each instance's contact read-out (k_contacts,
+    # -DMG_CONTACTS_TU: a test aid in code objects of its own, linked last, so the code objects before them are
+    # byte for byte what they are without it)
+    for j in range(-1, 2 * ninst):
+        i = j if j < ninst else j - ninst
+        o = os.path.join(objdir, "migym.o" if j < 0 else (f"inst{i}.o" if j < ninst else f"contacts{i}.o"))
+        src = SRC if j < 0 else INST
         # instance TUs: no MachineLICM.  The work-queue kernels' per-item body sits in a loop, and the pass hoists
         # values out of it into registers held across all items (Humanoid: 48 spilled VGPRs vs 25 without it;
         # measured +3 % ShadowHand, +2 % egg, +1 % Humanoid, Ant unchanged)
@@ -88,7 +94,9 @@ def build(force=False, verbose=False, timing=False, variant=None, defines=(), ex
         # round 3 with IPRA on -- wrong object states -- and, with the cause not pinned down, with IPRA off too:
         # an illegal address and a 93 % parity build).  Every phase is force-inlined, and
         # codeobj.check_no_calls below fails the build if any call is left in the device code
-        inst = [] if i < 0 else [f"-DMG_INST={i}", "-mllvm", "-disable-machine-licm", "-mllvm", "-enable-ipra=false"]
+        inst = [] if j < 0 else [f"-DMG_INST={i}", "-mllvm", "-disable-machine-licm", "-mllvm", "-enable-ipra=false"]
+        if j >= ninst:
+            inst.append("-DMG_CONTACTS_TU")
         cmds.append([hipcc] + flags + inst + ["-c", "-o", o, src])
         objs.append(o)
     _run_parallel(cmds, verbose)

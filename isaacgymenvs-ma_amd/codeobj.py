@@ -136,8 +136,9 @@ def diff(old_so, new_so, arch="gfx950"):
     list is the same machine code, which is what a source change meant to move none has to show.  A function counts
     as different when its instructions or their encodings do, not when it merely sits at another address behind
     one that grew.  A code object that only one library has is listed with every function it holds."""
-    def body(lines):  # a function's instructions and encodings: without its header line and the address column
-        return [re.sub(r"// [0-9A-F]+:", "//", line) for line in lines[1:]]
+    def body(lines):  # a function's instructions and encodings: without its header line and the address column,
+        # and without the blank and "..." lines objdump prints for the padding up to whatever function follows
+        return [re.sub(r"// [0-9A-F]+:", "//", line) for line in lines[1:] if line.strip() not in ("", "...")]
 
     def sect(co, name):
         try:

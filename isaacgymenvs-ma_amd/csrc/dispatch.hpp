@@ -45,6 +45,11 @@ struct RunEnvStep {
   static int run(hipStream_t s, const mg_sim* sim, const mg_task_params* tp, const mg_task_buffers* tb,
                  const mg_replay* rp);
 };
+// the first substep's contact list (k_contacts; mg_debug_contacts, tests only): non-DR, PGS
+template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY>
+struct RunContacts {
+  static int run(hipStream_t s, const mg_sim* sim, float* out, int32_t* count, int32_t cap);
+};
 // phase-timing build: publish the per-wave accumulator buffer to instance I's code object
 template <int I>
 int phase_buf_publish(unsigned long long* buf);

@@ -1,5 +1,7 @@
 // inst.hip — one capacity instance of the team kernels per translation unit (build.py compiles this
 // file once per -DMG_INST=i, i < MG_NUM_INST, in parallel, and links the objects with migym.hip).
+// With -DMG_CONTACTS_TU the unit holds the instance's contact read-out alone (k_contacts, mg_debug_contacts: tests
+// only) -- a code object of its own, so that the shipped instances' code objects are what they are without it.
 #include "step_kernels.hpp"
 
 #ifndef MG_INST
@@ -9,8 +11,12 @@ static_assert(MG_INST >= 0 && MG_INST < MG_NUM_INST, "MG_INST out of range");
 
 namespace mgi {
 constexpr InstDesc kI = kInst[MG_INST];
+#ifdef MG_CONTACTS_TU
+template struct RunContacts<kI.T, kI.MN, kI.MC, kI.MG, kI.MP, kI.OBJ, kI.LAY>;
+#else
 template struct BuildTile<kI.T, kI.MN, kI.MC, kI.MG, kI.MP, kI.OBJ, kI.LAY>;
 template struct RunSimulate<kI.T, kI.MN, kI.MC, kI.MG, kI.MP, kI.OBJ, kI.LAY>;
 template struct RunEnvStep<kI.T, kI.MN, kI.MC, kI.MG, kI.MP, kI.OBJ, kI.LAY>;
 template int phase_buf_publish<MG_INST>(unsigned long long*);
+#endif
 }  // namespace mgi

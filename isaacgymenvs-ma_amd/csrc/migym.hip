@@ -715,6 +715,19 @@ int mg_sim_simulate(mg_sim* sim, void* stream) {
   return check_launch("mg_sim_simulate");
 }
 
+// Tests only: the contact list the first substep of mg_sim_simulate would build from the bound state (k_contacts,
+// the instance and layout mg_sim_simulate's dispatch picks); the DR and TGS instances have no read-out
+int mg_debug_contacts(mg_sim* sim, float* out, int32_t* count, int32_t cap, void* stream) {
+  if (!sim || !sim->bound) return fail(MG_EINVAL, "mg_debug_contacts: sim not bound");
+  if (!out || !count || cap < 0) return fail(MG_EINVAL, "mg_debug_contacts: bad arguments");
+  if (sim->views.env_props || sim->params.solver_type != MG_SOLVER_PGS)
+    return fail(MG_EINVAL, "mg_debug_contacts: no read-out of the domain-randomized or TGS instances");
+  int rc = mgi::dispatch<mgi::RunContacts>(sim->host_model, sim->params.max_contacts, sim->layout_n, (hipStream_t)stream,
+                                           (const mg_sim*)sim, out, count, cap);
+  if (rc) return rc;
+  return check_launch("mg_debug_contacts");
+}
+
 int mg_sim_set_params(mg_sim* sim, const mg_sim_params* params) {
   if (!sim || !params || params->substeps < 1 || params->dt <= 0.0f || params->max_contacts < 0)
     return fail(MG_EINVAL, "mg_sim_set_params: bad arguments");

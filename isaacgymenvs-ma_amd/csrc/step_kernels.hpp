@@ -198,6 +198,67 @@ __global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, OBJ, DR, LAY>::kThreads))
   }
 }
 
+// mg_debug_contacts (tests only): the contact list of the first substep of k_simulate, per actor.  The same Team,
+// LDS layout, model tile, init / load and launch shape as k_simulate above, and the front half of
+// Team::substep() up to collide() -- THE CALL SEQUENCE BELOW REPEATS Team::substep()'s (team_physics.hpp): change
+// both together.  Rows (nodeA, geomA, nodeB, geomB, p[3], n[3], gap) as the oracle's orc_contacts_full; the ids
+// sign-extended from cside (-1 ground, -2 the object).  Nothing is written back to the state views.
+template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY = 0>
+__global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, OBJ, false, LAY>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, OBJ, false, LAY>::kWPE))) void k_contacts(
+    const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n,
+    float* __restrict__ out, int* __restrict__ count, int cap) {
+  using SH = Shape<T, MN, MC, MG, MP, OBJ, false, LAY>;
+  constexpr int E = SH::E;
+  constexpr int ROWS = OBJ ? 3 : 1;
+  __shared__ mg::BankSlot<mg::TeamLDSOf<T, MN, MC, OBJ, MG, MP, LAY>, T> lds[E];
+  __shared__ typename mg::Team<T, MN, MC, MG, MP, OBJ>::MT tile;
+  mg::copy_tile(&tile, static_cast<const typename mg::Team<T, MN, MC, MG, MP, OBJ>::MT*>(timg));
+  __syncthreads();
+  const int team = threadIdx.x / T;
+  const int a = blockIdx.x * E + team;
+  const bool valid = a < n;
+  const int ac = valid ? a : n - 1;
+  const int nd = m->num_dofs;
+  mg::Team<T, MN, MC, MG, MP, OBJ, false, LAY> t;
+  t.init(&lds[team].v, &tile, m, &p);
+  if (OBJ && t.tl < 4) {
+    const float* fr = v.rb_forces ? v.rb_forces + ((size_t)(m->num_bodies + 2) * ac + m->num_bodies) * 3 : nullptr;
+    lds[team].v.oforce[t.tl] = t.tl < 3 ? (fr ? fr[t.tl] : 0.0f) : (v.rb_force_space == MG_LOCAL_SPACE ? 1.0f : 0.0f);
+  }
+  mg::wsync();
+  float* root = v.root_states + (size_t)13 * ROWS * ac;
+  t.load(root, v.dof_state + (size_t)2 * nd * ac, v.dof_actuation ? v.dof_actuation + (size_t)nd * ac : nullptr,
+         OBJ ? root + 13 : nullptr, v.dof_targets ? v.dof_targets + (size_t)nd * ac : nullptr);
+  t.hull_stage();
+  t.fk();
+  if constexpr (OBJ == MG_GT_ELLIPSOID) {
+    t.egg_stage();
+    t.reload_tree();
+  }
+  t.set_axis();
+  if (OBJ) t.tendons();
+  t.aba();
+  t.obj_free();
+  t.collide();  // ends with a wave sync: s->ncon and the list are visible to the team
+  if (valid) {
+    auto& L = lds[team].v;
+    const int nc = L.ncon;
+    if (t.tl == 0) count[a] = nc;
+    for (int c = t.tl; c < nc && c < cap; c += T) {
+      float* o = out + ((size_t)a * cap + c) * 11;
+      o[0] = (float)t.cside(c, 0);
+      o[1] = (float)t.cside(c, 2);
+      o[2] = (float)t.cside(c, 1);
+      o[3] = (float)t.cside(c, 3);
+      for (int k = 0; k < 3; k++) {
+        o[4 + k] = L.cp[c][k];
+        o[7 + k] = L.cn[c][k];
+      }
+      o[10] = L.gap(c);
+    }
+  }
+}
+
 // The whole VecTask.step for one actor, fused: clamp -> actuation -> simulate -> post_physics.
 // One team of T lanes per actor; the team leader (tl == 0) runs the task layer on the LDS-staged
 // state, the team writes it back to HBM.  Multi-agent: the agents of an env are consecutive
@@ -898,6 +959,18 @@ int RunSimulate<T, MN, MC, MG, MP, OBJ, LAY>::run(hipStream_t s, const mg_sim* s
     launch<Shape<T, MN, MC, MG, MP, OBJ, false, LAY>>(k_simulate<T, MN, MC, MG, MP, OBJ, false, false, LAY>, s, sim->n, sim->d_model,
                                                   (const void*)sim->d_tile, sim->params, sim->views, sim->n);
   }
+  return MG_OK;
+}
+
+template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY>
+int RunContacts<T, MN, MC, MG, MP, OBJ, LAY>::run(hipStream_t s, const mg_sim* sim, float* out, int32_t* count, int32_t cap) {
+  if (!sim->d_tile) return fail(MG_ECAPACITY, "mg_debug_contacts: no model tile (model exceeds every kernel instance)");
+  // the most contacts the kernel's collide() keeps for an actor
+  const int kept = sim->params.max_contacts < MC ? sim->params.max_contacts : MC;
+  if (cap < kept) return fail(MG_EINVAL, "mg_debug_contacts: cap is below the kernel's contact count");
+  launch<Shape<T, MN, MC, MG, MP, OBJ, false, LAY>>(k_contacts<T, MN, MC, MG, MP, OBJ, LAY>, s, sim->n, sim->d_model,
+                                                    (const void*)sim->d_tile, sim->params, sim->views, sim->n, out, count,
+                                                    (int)cap);
   return MG_OK;
 }
 

@@ -2528,6 +2528,8 @@ struct Team {
   }
 
   // ---------------------------------------------------------------- one substep
+  // (step_kernels.hpp k_contacts repeats the sequence below up to collide(), less root_coupling(), which writes
+  // nothing collide() reads: change both together)
   __device__ __forceinline__ void substep() {
     ph_mark(15);
     hull_stage();

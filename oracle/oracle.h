@@ -52,6 +52,11 @@ int orc_free_acceleration(const mg_model* m, const mg_sim_params* p, const float
  * (node, px,py,pz, nx,ny,nz, depth, nodeB) records of 9 doubles */
 int orc_contacts(const mg_model* m, const mg_sim_params* p, const float* root13, const float* dof2, double* out,
                  int32_t cap);
+/* orc_contacts_full's records (nodeA, geomA, nodeB, geomB, p(3), n(3), d) with a 12th column of marks, thresholds moved out by delta (1 ambiguous pair, 2 ill-conditioned
+ * normal, 4 within delta below its threshold, 8 at or above it); *pair_lost: an ambiguous decision left a
+ * geom-object pair without a contact */
+int orc_contacts_marks(const mg_model* m, const mg_sim_params* p, const float* root13, const float* dof2, double delta,
+                       double* out, int32_t cap, int32_t* pair_lost);
 /* egg narrowphase KAT hook (GJK + shrunk-core retry): kind 0 segment p0,p1 / kind 1 box c, R (row-major),
  * h, plus radius, vs the origin-centred ellipsoid e; out = point(3), normal(3), distance */
 int orc_ellipsoid_contact(int32_t kind, const double* shape, double radius, const double* e, double* out);

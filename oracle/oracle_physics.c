@@ -68,6 +68,7 @@ static __thread int orc_tie_hit = 0;
 static __thread int orc_amb_hit = 0;  /* bit 16 for the whole step (an ambiguous decision that made no contact) */
 static __thread int orc_amb_pend = 0; /* an ambiguous decision in the current geom-object candidate set */
 static __thread int orc_ill_next = 0;
+static __thread int orc_edge_next = 0; /* the contact being pushed is box_box_edge's */
 static __thread int orc_pb_ill = 0;   /* the last point_box: outside, two or more axes clamped, nearer than NORMAL_ILL */
 static __thread int orc_cvx_ill = 0;  /* the last cvx_contact: an MPR depth below NORMAL_ILL */
 static __thread int orc_hull_ill = 0; /* the last hull_core_contacts: a GJK distance below NORMAL_ILL */
@@ -200,6 +201,7 @@ typedef struct {
   real p[3], n[3], d;
   int ill;   /* ill-conditioned normal (orc_step_flips bit 32) */
   int amb;   /* made by a geom-object candidate set with a decision in its ambiguity band (bit 16) */
+  int edge;  /* box_box_edge's contact (orc_contacts_marks bit 16: what a state set reaches) */
 } contact;
 
 static int nv_of(const mg_model* m) { return (m->fixed_base ? 0 : 6) + m->num_dofs; }
@@ -485,7 +487,9 @@ static int push_contact(contact* out, int n, int cap, int nodeA, int gA, int nod
   c->d = d;
   c->ill = orc_ill_next;
   c->amb = 0;
+  c->edge = orc_edge_next;
   orc_ill_next = 0;
+  orc_edge_next = 0;
   return n + 1;
 }
 
@@ -914,7 +918,9 @@ static int geom_object(const mg_model* m, const kin* k, int g, real off, contact
       real pw[3], nw[3];
       from_obj_pt(k, pe, pw);
       from_obj_dir(k, ne, nw);
+      orc_edge_next = 1;
       n = push_contact(out, n, cap, nd, g, OBJ_NODE, -2, pw, nw, de);
+      orc_edge_next = 0;
     }
   }
   return n;
@@ -2970,6 +2976,49 @@ int orc_contacts_full(const mg_model* m, const mg_sim_params* p, const float* ro
 }
 
 #ifndef ORC_FP32 /* fp64 inspection hooks of the checker (KATs); not in the fp32 timing build */
+/* orc_contacts_full's rows with a 12th column of marks, for the contact-level comparison (tests/contacts_ref.py).
+ * The list is collide()'s with every contact threshold moved out by `delta` (the contact offset and the MJCF pairs'
+ * zero distance, as orc_step_flips moves them) and the narrowphase's ambiguity bands armed, so that it also holds
+ * the candidates an fp32 implementation may or may not emit.  Marks (bits):
+ *   1  made by a geom-object candidate set with a decision inside its ambiguity band (contact.amb)
+ *   2  ill-conditioned normal (contact.ill: orc_pb_ill / orc_cvx_ill / orc_hull_ill, NORMAL_ILL)
+ *   4  gap within delta of its threshold, below it (the contact is in orc_contacts_full's list)
+ *   8  gap at or above its threshold (only the widened list holds it)
+ *  16  box_box_edge's contact (not an exemption: what the state sets must reach)
+ * *pair_lost = 1 when an ambiguous decision left a geom-object pair without any contact.  Returns the count. */
+int orc_contacts_marks(const mg_model* m, const mg_sim_params* p, const float* root13, const float* dof2, double delta,
+                       double* out, int32_t cap, int32_t* pair_lost) {
+  astate s;
+  kin k;
+  memset(&s, 0, sizeof(s));
+  load_state(m, root13, dof2, &s);
+  if (m->obj_type) load_object(&s, root13 + 13);
+  forward_kinematics(m, &s, &k);
+  contact con[MAXC];
+  mg_sim_params pw = *p;
+  pw.contact_offset = (float)(p->contact_offset + delta);
+  orc_pair_offset = delta;
+  orc_tie_delta = delta;
+  orc_amb_hit = 0;
+  int nc = collide(m, &pw, &k, con, cap < MAXC ? cap : MAXC);
+  orc_pair_offset = 0.0;
+  orc_tie_delta = -1.0;
+  if (pair_lost) *pair_lost = orc_amb_hit;
+  orc_amb_hit = 0;
+  for (int i = 0; i < nc; i++) {
+    real* o = out + 12 * i;
+    o[0] = con[i].nodeA; o[1] = con[i].geomA; o[2] = con[i].nodeB; o[3] = con[i].geomB;
+    for (int a = 0; a < 3; a++) { o[4 + a] = con[i].p[a]; o[7 + a] = con[i].n[a]; }
+    o[10] = con[i].d;
+    const real thr = (m->pair_mjcf && con[i].nodeB >= 0) ? 0.0 : p->contact_offset;
+    int mk = (con[i].amb ? 1 : 0) | (con[i].ill ? 2 : 0) | (con[i].edge ? 16 : 0);
+    if (!(con[i].d < thr)) mk |= 8;
+    else if (thr - con[i].d < delta) mk |= 4;
+    o[11] = mk;
+  }
+  return nc;
+}
+
 /* The discontinuities of the build's physics that env `e`'s gym.simulate (state views as orc_simulate_views)
  * passes near, substep by substep (tests/parity_stats.py): an fp32 and an fp64 step of the same state may part
  * ways there, and nowhere else.  Each substep is solved once more with the thresholds moved out by `delta` (the

@@ -42,6 +42,7 @@ def lib():
         l.orc_free_acceleration.argtypes = [P, C.POINTER(_abi.SimParams), P, P, P, P]
         l.orc_contacts.argtypes = [P, C.POINTER(_abi.SimParams), P, P, P, C.c_int32]
         l.orc_contacts_full.argtypes = [P, C.POINTER(_abi.SimParams), P, P, P, C.c_int32]
+        l.orc_contacts_marks.argtypes = [P, C.POINTER(_abi.SimParams), P, P, C.c_double, P, C.c_int32, P]
         l.orc_rigid_body_states.argtypes = [P, P, P, P]
         l.orc_compute_observations.argtypes = [C.POINTER(_abi.TaskParams), C.c_int32] + [P] * 10
         l.orc_compute_reward.argtypes = [C.POINTER(_abi.TaskParams), C.c_int32] + [P] * 7
@@ -89,6 +90,7 @@ def lib_f32():
         l.orc_simulate.argtypes = [P, C.POINTER(_abi.SimParams), C.c_int32, P, P, P, P, P, C.c_int32]
         l.orc_simulate_views.argtypes = [P, C.POINTER(_abi.SimParams), C.c_int32, C.POINTER(_abi.StateViews),
                                          C.c_int32]
+        l.orc_contacts_full.argtypes = [P, C.POINTER(_abi.SimParams), P, P, P, C.c_int32]   # rows of 11 floats
         _lib32 = l
     return _lib32
 
@@ -130,12 +132,25 @@ def contacts(model_np, sp, root13, dof2, cap=64):
     return out[: 9 * n].reshape(n, 9)
 
 
-def contacts_full(model_np, sp, root13, dof2, cap=64):
+def contacts_full(model_np, sp, root13, dof2, cap=64, fp32=False):
     """the contact candidates with both geoms: rows (nodeA, geomA, nodeB, geomB, p(3), n(3), d); nodeB / geomB < 0
-    against the ground"""
-    out = np.zeros(11 * cap)
-    n = lib().orc_contacts_full(model_np.ctypes.data, C.byref(sp), p(f32(root13)), p(f32(dof2)), p(out), cap)
-    return out[: 11 * n].reshape(n, 11)
+    against the ground.  fp32: the oracle's fp32 twin (rows of floats, returned as float64)"""
+    out = np.zeros(11 * cap, np.float32 if fp32 else np.float64)
+    n = (lib_f32() if fp32 else lib()).orc_contacts_full(model_np.ctypes.data, C.byref(sp), p(f32(root13)),
+                                                         p(f32(dof2)), p(out), cap)
+    return out[: 11 * n].reshape(n, 11).astype(np.float64)
+
+
+def contacts_marks(model_np, sp, root13, dof2, delta=1e-4, cap=64):
+    """(rows, marks, pair_lost) of orc_contacts_marks: collide()'s list with the thresholds moved out by delta, rows as
+    contacts_full; marks per row (1 ambiguous pair, 2 ill-conditioned normal, 4 within delta below the threshold,
+    8 at or above the threshold); pair_lost: an ambiguous decision left a geom-object pair without a contact"""
+    out = np.zeros(12 * cap)
+    lost = np.zeros(1, np.int32)
+    n = lib().orc_contacts_marks(model_np.ctypes.data, C.byref(sp), p(f32(root13)), p(f32(dof2)), float(delta), p(out),
+                                 cap, p(lost))
+    r = out[: 12 * n].reshape(n, 12)
+    return r[:, :11].copy(), r[:, 11].astype(np.int32), bool(lost[0])
 
 
 def box_box_edge(c, R, h, hb, off):
