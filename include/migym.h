@@ -579,6 +579,80 @@ typedef struct mg_osc_args {
 int mg_osc_torques(mg_sim* sim, const mg_osc_args* args, void* stream);
 size_t mg_osc_args_sizeof(void);
 
+/* ---- FrankaReachMA (franka_reach_MA.py): the multi-arm OSC reach task as three launches per control step --
+ * mg_reach_pre, mg_sim_simulate x controlFrequencyInv, mg_reach_post -- all asynchronous on the caller's stream.
+ * A arms per env (independent fixed-base articulations, actor = env * A + agent) and T <= A target cubes per env; the
+ * cubes are task-owned state that only a reset moves (the reference masks them out of arm collisions and switches
+ * their gravity off, franka_reach_MA.py:287, 363, 384).  New structs only: the step kernels and their argument
+ * structs are untouched, and mg_task_buffers is reused for the VecTask buffers. */
+typedef struct mg_reach_params {
+  int32_t num_agents;          /* A: 1..MG_MAX_AGENTS */
+  int32_t num_targets;         /* T: 1..A */
+  int32_t num_obs;             /* 10 + 3 T + 3 (A - 1) */
+  int32_t max_episode_length;
+  float clip_actions, clip_obs;
+  float action_scale;          /* dpose = (clamp(a) * cmd_limit) / action_scale (franka_reach_MA.py:812) */
+  float cmd_limit[6];
+  /* the OSC gains, null-space defaults and effort limits, as mg_osc_args carries them */
+  float kp[6], kd[6];
+  float kp_null[7], kd_null[7];
+  float osc_default_dof_pos[7];
+  float effort_limit[7];
+  int32_t jac_body;            /* panda_hand: the body whose Jacobian rows drive the controller */
+  int32_t eef_body;            /* panda_grip_site: the end effector (observations, eef_vel) */
+  int32_t hand_body;           /* panda_hand: the net_contact_forces row of the -10 punishment */
+  int32_t num_bodies;          /* rigid-body rows per arm */
+  int32_t num_dofs;            /* DOFs per arm (9: 7 arm joints, 2 fingers) */
+  float default_dof_pos[9];    /* franka_default_dof_pos */
+  float dof_lower[9], dof_upper[9];
+  float dof_noise_scale;       /* frankaDofNoise * 2.0 (the reference multiplies the Python floats first) */
+  float cube_xy_center[2];     /* _table_surface_pos[:2] */
+  float cube_xy_scale;         /* 2.0 * startPositionNoise */
+  float cube_z_base;           /* _table_surface_pos[2] + cubeA_size / 2, summed in fp32 as the reference's tensors */
+  float cube_z_range;          /* rand_z_range (0.5) */
+} mg_reach_params;
+
+/* task-owned device tensors */
+typedef struct mg_reach_views {
+  float* cube_states;          /* (N, T, 13) _cubeA_state */
+  float* init_cube_states;     /* (N, T, 13) _init_cubeA_state */
+  float* dof_targets;          /* (N*A*nD) _pos_control: the buffer the sim has bound as dof_targets */
+  float* dof_actuation;        /* (N*A*nD) _effort_control: the buffer the sim has bound as dof_actuation */
+} mg_reach_views;
+size_t mg_reach_params_sizeof(void);
+size_t mg_reach_views_sizeof(void);
+
+/* mg_task_buffers fields the reach entry points use: actions (N*A, 6), actions_out, obs, obs_clamped, rew, reset,
+ * progress, timeout, noise, seed, step_counter, env_offset, out_pack.  noise: (N, 3 T + 9) U(0,1) per env, in the
+ * reference's draw order [z of each cube (T) | xy of each cube (2 T) | DOF noise (9)] (franka_reach_MA.py:692, 696,
+ * 631); NULL = the counter RNG keyed by (seed, env_offset + env, step_counter, column). */
+
+/* pre_physics_step (franka_reach_MA.py:804-819), one launch, per arm: actions_out = clamp(actions, +-clip_actions),
+ * dpose = (actions_out * cmd_limit) / action_scale, the OSC torques of mg_osc_torques (J of jac_body, the leading
+ * 7 x 7 of the full tree's M, eef_vel read in place from columns 7:13 of eef_body's row of the bound
+ * rigid_body_states, clamped to effort_limit) written into columns 0..5 of the arm's dof_actuation row: the reference
+ * writes _arm_control[:, :6], so joint 7's entry stays what the last reset left (0).  An arm whose factorisation fails
+ * gets zeros (mg_osc_torques's contract). */
+int mg_reach_pre(mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* views, const mg_task_buffers* tb,
+                 void* stream);
+
+/* post_physics_step + the VecTask.step tail (franka_reach_MA.py:821-829, 616-679; vec_task.py step tail), one launch,
+ * per env: progress += 1; the env resets when all A agents have reset != 0 (cubes, DOF state, targets, actuation,
+ * progress and reset cleared; the same 9 DOF draws go to every arm); observations [cube positions 3 T | eef_quat 4 |
+ * eef_pos 3 | nearest cube - eef 3 | the other agents' eef_pos, cyclic 3 (A - 1)] with the eef taken from
+ * rigid_body_states as simulate left it (not recomputed after a reset: gym refreshes that tensor in simulate only);
+ * compute_franka_reward; reset = 1 at progress >= max_episode_length - 1; timeout, obs clamp, out_pack.
+ * state: NULL = the sim's bound views; else its dof_state, rigid_body_states and net_contact_forces are taken as the
+ * post-simulate state (physics-free replay; dof_state is written by a reset). */
+int mg_reach_post(mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* views, const mg_task_buffers* tb,
+                  const mg_state_views* state, void* stream);
+
+/* reset_idx(agent_ids) now (franka_reach_MA.py:616-679): the envs the AND filter of the n agent ids selects
+ * (bincount(ids // A) >= A: a repeated id counts twice) get the reset of mg_reach_post.  Noise: tb->noise rows by env,
+ * or the counter RNG on the manual-reset stream (step_counter | 2^62), as mg_reset_idx. */
+int mg_reach_reset_idx(mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* views,
+                       const mg_task_buffers* tb, const int32_t* ids, int32_t n, void* stream);
+
 /* Measurement aid (no reference counterpart; bench.py's roofline.kernel_ms): the device-side duration of the
  * fused step kernel, from the first wave's start to the last wave's end on the GPU's constant wall clock
  * (wall_clock64, hipDeviceAttributeWallClockRate), so that no launch, queue or event-packet overhead is in it.

@@ -396,10 +396,18 @@ __device__ __forceinline__ bool osc_solve(const float (&M)[kOscMax][kOscMax], co
   return ok;
 }
 
-// task-space command w and null-space torque un of one actor; DOFs past arm_dofs get zero
-__device__ __forceinline__ void osc_inputs(const OscParams& p, int actor, const float* __restrict__ dof,
-                                           float (&w)[6], float (&un)[kOscMax]) {
-  const float* dp = p.dpose + (size_t)6 * actor;
+// where the team kernel takes an actor's dpose from when it is not p.dpose: the policy's action row
+// (FrankaReachMA.pre_physics_step, franka_reach_MA.py:804-812; mg_reach_pre)
+struct OscActions {
+  const float* actions;   // (n, 6) raw actions
+  float* actions_out;     // (n, 6) clamp(actions, +-clip_actions), or nullptr
+  float clip_actions, action_scale;
+  float cmd_limit[6];
+};
+
+// task-space command w and null-space torque un of one actor from its dpose row dp; DOFs past arm_dofs get zero
+__device__ __forceinline__ void osc_inputs(const OscParams& p, const float* dp, int actor,
+                                           const float* __restrict__ dof, float (&w)[6], float (&un)[kOscMax]) {
   const float* ev = p.eef_vel + (size_t)p.eef_vel_stride * actor;
 #pragma unroll
   for (int a = 0; a < 6; a++) w[a] = p.kp[a] * dp[a] - p.kd[a] * ev[a];
@@ -414,16 +422,87 @@ __device__ __forceinline__ void osc_inputs(const OscParams& p, int actor, const 
   }
 }
 
-// INJECT: one lane per actor on the caller's J and M.  Otherwise one team per actor: J's row and M's leading block
-// are built in LDS from the state (the full tree's composites, so the gripper's inertia is in M) and never leave it.
+// One team per actor: J's row and M's leading block are built in LDS from the state (the full tree's composites, so
+// the gripper's inertia is in M) and never leave it.  ACT: dpose comes from the actor's action row (oa), clamped and
+// scaled in the reference's operation order, and the clamped actions are written out; otherwise from p.dpose.  The
+// body of k_osc<false> and of k_reach_pre (reach_task.hpp): one device code for both.
+template <bool ACT>
+__device__ __forceinline__ void osc_team(const DynModel* __restrict__ gm, int n, const OscParams& p,
+                                         const float* __restrict__ root_states, const float* __restrict__ dof_state,
+                                         const float* __restrict__ env_props, int props_stride,
+                                         const OscActions* oa) {
+  const int na = p.arm_dofs;
+  float M[kOscMax][kOscMax], J[6][kOscMax], w[6], un[kOscMax], u[kOscMax];
+  __shared__ DynModel m;
+  extern __shared__ float team_lds[];   // scratch_bytes(num_nodes)
+  __shared__ float MJ[kTeams][kOscMax * kOscMax + 6 * kOscMax];
+  stage_model(&m, gm);
+  __syncthreads();
+  const int team = threadIdx.x / kTeam, tl = threadIdx.x % kTeam;
+  const int actor = blockIdx.x * kTeams + team;
+  const bool live = actor < n;
+  const int ac = live ? actor : 0;
+  const TeamScratch tsv = team_scratch(team_lds, m.num_nodes, team);
+  const TeamScratch* ts = &tsv;
+  const float* dof = dof_state + (size_t)2 * p.nd * ac;
+  team_fk_crba(&m, ts, tl, live, root_states + (size_t)13 * ac, dof,
+               env_props ? env_props + (size_t)props_stride * ac : nullptr);
+  team_forces(&m, ts, tl, live, na);
+  if (live) {
+    float* mj = MJ[team];
+    for (int e = tl; e < kOscMax * kOscMax; e += kTeam) {
+      const int i = e / kOscMax, j = e - i * kOscMax;
+      mj[e] = (i < na && j < na) ? mass_entry(&m, ts, i, j) : (i == j ? 1.0f : 0.0f);
+    }
+    for (int e = tl; e < 6 * kOscMax; e += kTeam) {
+      const int a = e / kOscMax, j = e - a * kOscMax;
+      mj[kOscMax * kOscMax + e] = j < na ? jac_entry(&m, ts, p.jac_body, a, j) : 0.0f;
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  // every lane of the team runs the small dense solve on the same LDS values (broadcast reads): the lanes hold
+  // identical u, and lane i writes torque i
+  const float* mj = MJ[team];
+#pragma unroll
+  for (int i = 0; i < kOscMax; i++)
+#pragma unroll
+    for (int j = 0; j < kOscMax; j++) M[i][j] = mj[i * kOscMax + j];
+#pragma unroll
+  for (int a = 0; a < 6; a++)
+#pragma unroll
+    for (int j = 0; j < kOscMax; j++) J[a][j] = mj[kOscMax * kOscMax + a * kOscMax + j];
+  if constexpr (ACT) {
+    float dp[6];   // a product then a quotient: nothing here for FMA contraction to fuse
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      float a = oa->actions[(size_t)6 * actor + c];
+      a = a < oa->clip_actions ? a : oa->clip_actions;
+      a = a > -oa->clip_actions ? a : -oa->clip_actions;
+      if (oa->actions_out && tl == c) oa->actions_out[(size_t)6 * actor + c] = a;
+      dp[c] = (a * oa->cmd_limit[c]) / oa->action_scale;
+    }
+    osc_inputs(p, dp, actor, dof, w, un);
+  } else {
+    osc_inputs(p, p.dpose + (size_t)6 * actor, actor, dof, w, un);
+  }
+  const bool ok = osc_solve(M, J, w, un, u);
+  float v = 0.0f, lim = 0.0f;
+#pragma unroll
+  for (int i = 0; i < kOscMax; i++)
+    if (tl == i) { v = u[i]; lim = p.effort_limit[i]; }
+  if (tl < p.out_cols) p.out[(size_t)p.out_stride * actor + tl] = ok ? fminf(fmaxf(v, -lim), lim) : 0.0f;
+}
+
+// INJECT: one lane per actor on the caller's J and M.  Otherwise one team per actor (osc_team).
 template <bool INJECT>
 __global__ __launch_bounds__(64) void k_osc(const DynModel* __restrict__ gm, int n, OscParams p,
                                             const float* __restrict__ root_states,
                                             const float* __restrict__ dof_state,
                                             const float* __restrict__ env_props, int props_stride) {
-  const int na = p.arm_dofs;
-  float M[kOscMax][kOscMax], J[6][kOscMax], w[6], un[kOscMax], u[kOscMax];
   if constexpr (INJECT) {
+    const int na = p.arm_dofs;
+    float M[kOscMax][kOscMax], J[6][kOscMax], w[6], un[kOscMax], u[kOscMax];
     const int actor = blockIdx.x * blockDim.x + threadIdx.x;
     if (actor >= n) return;
     const float* mi = p.mm_in + (size_t)na * na * actor;
@@ -436,59 +515,14 @@ __global__ __launch_bounds__(64) void k_osc(const DynModel* __restrict__ gm, int
     for (int a = 0; a < 6; a++)
 #pragma unroll
       for (int j = 0; j < kOscMax; j++) J[a][j] = j < na ? ji[a * na + j] : 0.0f;
-    osc_inputs(p, actor, dof_state + (size_t)2 * p.nd * actor, w, un);
+    osc_inputs(p, p.dpose + (size_t)6 * actor, actor, dof_state + (size_t)2 * p.nd * actor, w, un);
     const bool ok = osc_solve(M, J, w, un, u);
     float* o = p.out + (size_t)p.out_stride * actor;
 #pragma unroll
     for (int i = 0; i < kOscMax; i++)
       if (i < p.out_cols) o[i] = ok ? fminf(fmaxf(u[i], -p.effort_limit[i]), p.effort_limit[i]) : 0.0f;
   } else {
-    __shared__ DynModel m;
-    extern __shared__ float team_lds[];   // scratch_bytes(num_nodes)
-    __shared__ float MJ[kTeams][kOscMax * kOscMax + 6 * kOscMax];
-    stage_model(&m, gm);
-    __syncthreads();
-    const int team = threadIdx.x / kTeam, tl = threadIdx.x % kTeam;
-    const int actor = blockIdx.x * kTeams + team;
-    const bool live = actor < n;
-    const int ac = live ? actor : 0;
-    const TeamScratch tsv = team_scratch(team_lds, m.num_nodes, team);
-    const TeamScratch* ts = &tsv;
-    const float* dof = dof_state + (size_t)2 * p.nd * ac;
-    team_fk_crba(&m, ts, tl, live, root_states + (size_t)13 * ac, dof,
-                 env_props ? env_props + (size_t)props_stride * ac : nullptr);
-    team_forces(&m, ts, tl, live, na);
-    if (live) {
-      float* mj = MJ[team];
-      for (int e = tl; e < kOscMax * kOscMax; e += kTeam) {
-        const int i = e / kOscMax, j = e - i * kOscMax;
-        mj[e] = (i < na && j < na) ? mass_entry(&m, ts, i, j) : (i == j ? 1.0f : 0.0f);
-      }
-      for (int e = tl; e < 6 * kOscMax; e += kTeam) {
-        const int a = e / kOscMax, j = e - a * kOscMax;
-        mj[kOscMax * kOscMax + e] = j < na ? jac_entry(&m, ts, p.jac_body, a, j) : 0.0f;
-      }
-    }
-    __syncthreads();
-    if (!live) return;
-    // every lane of the team runs the small dense solve on the same LDS values (broadcast reads): the lanes hold
-    // identical u, and lane i writes torque i
-    const float* mj = MJ[team];
-#pragma unroll
-    for (int i = 0; i < kOscMax; i++)
-#pragma unroll
-      for (int j = 0; j < kOscMax; j++) M[i][j] = mj[i * kOscMax + j];
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-      for (int j = 0; j < kOscMax; j++) J[a][j] = mj[kOscMax * kOscMax + a * kOscMax + j];
-    osc_inputs(p, actor, dof, w, un);
-    const bool ok = osc_solve(M, J, w, un, u);
-    float v = 0.0f, lim = 0.0f;
-#pragma unroll
-    for (int i = 0; i < kOscMax; i++)
-      if (tl == i) { v = u[i]; lim = p.effort_limit[i]; }
-    if (tl < p.out_cols) p.out[(size_t)p.out_stride * actor + tl] = ok ? fminf(fmaxf(v, -lim), lim) : 0.0f;
+    osc_team<false>(gm, n, p, root_states, dof_state, env_props, props_stride, nullptr);
   }
 }
 

@@ -10,6 +10,7 @@
 
 #include "dispatch.hpp"
 #include "dynamics_tensors.hpp"
+#include "reach_task.hpp"   // before hand_task.hpp: that header leaves FMA contraction off for the rest of this file
 #include "hand_task.hpp"
 #include "task.hpp"
 
@@ -1265,5 +1266,102 @@ int mg_osc_torques(mg_sim* sim, const mg_osc_args* a, void* stream) {
   return check_launch("mg_osc_torques");
 }
 
+
+// ---- FrankaReachMA: the task layer around mg_sim_simulate (reach_task.hpp)
+size_t mg_reach_params_sizeof(void) { return sizeof(mg_reach_params); }
+size_t mg_reach_views_sizeof(void) { return sizeof(mg_reach_views); }
+
+// the shared argument check: a bound fixed-base sim whose model and actor count match the task constants
+static int reach_args_ok(const mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* v,
+                         const mg_task_buffers* tb, const char* who) {
+  if (int rc = dynamics_sim_ok(sim, who, true)) return rc;
+  if (!rp || !v || !tb) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
+  const int A = rp->num_agents, T = rp->num_targets;
+  if (A < 1 || A > MG_MAX_AGENTS || T < 1 || T > A)
+    return fail(MG_EINVAL, std::string(who) + ": num_agents must be 1..8 and num_targets 1..num_agents");
+  if (rp->num_obs != 10 + 3 * T + 3 * (A - 1))
+    return fail(MG_EINVAL, std::string(who) + ": num_obs must be 10 + 3 num_targets + 3 (num_agents - 1)");
+  if (sim->n % A != 0) return fail(MG_EINVAL, std::string(who) + ": the actor count is no multiple of num_agents");
+  const mg_model& m = sim->host_model;
+  if (rp->num_dofs != m.num_nodes - 1 || rp->num_dofs < 7 || rp->num_dofs > mgr::kReachDofs ||
+      rp->num_bodies != m.num_bodies)
+    return fail(MG_EINVAL, std::string(who) + ": num_dofs (7..9) / num_bodies do not match the sim's model");
+  if (rp->jac_body < 1 || rp->jac_body >= m.num_bodies || rp->eef_body < 0 || rp->eef_body >= m.num_bodies ||
+      rp->hand_body < 0 || rp->hand_body >= m.num_bodies)
+    return fail(MG_EINVAL, std::string(who) + ": jac_body / eef_body / hand_body out of range");
+  if (!v->cube_states || !v->init_cube_states || !v->dof_targets || !v->dof_actuation)
+    return fail(MG_EINVAL, std::string(who) + ": needs cube_states, init_cube_states, dof_targets and dof_actuation");
+  return MG_OK;
+}
+
+int mg_reach_pre(mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* views, const mg_task_buffers* tb,
+                 void* stream) {
+  if (int rc = reach_args_ok(sim, rp, views, tb, "mg_reach_pre")) return rc;
+  if (!tb->actions) return fail(MG_EINVAL, "mg_reach_pre: needs actions");
+  if (!sim->views.rigid_body_states)
+    return fail(MG_EINVAL, "mg_reach_pre: the sim needs rigid_body_states bound (eef_vel is read from it)");
+  if (!(rp->action_scale != 0.0f)) return fail(MG_EINVAL, "mg_reach_pre: action_scale must not be 0");
+  if (sim->n == 0) return MG_OK;
+  mgd::OscParams p;
+  p.arm_dofs = 7;
+  p.jac_body = rp->jac_body;
+  p.out_cols = 6;   // _arm_control[:, :6] (franka_reach_MA.py:817)
+  p.nd = rp->num_dofs;
+  p.dpose = nullptr;
+  p.eef_vel = sim->views.rigid_body_states + (size_t)13 * rp->eef_body + 7;
+  p.eef_vel_stride = (long long)13 * rp->num_bodies;
+  for (int k = 0; k < 6; k++) { p.kp[k] = rp->kp[k]; p.kd[k] = rp->kd[k]; }
+  for (int k = 0; k < mgd::kOscMax; k++) {
+    p.kp_null[k] = rp->kp_null[k];
+    p.kd_null[k] = rp->kd_null[k];
+    p.default_dof_pos[k] = rp->osc_default_dof_pos[k];
+    p.effort_limit[k] = rp->effort_limit[k];
+  }
+  p.out = views->dof_actuation;
+  p.out_stride = rp->num_dofs;
+  p.jac_in = nullptr;
+  p.mm_in = nullptr;
+  mgd::OscActions oa;
+  oa.actions = tb->actions;
+  oa.actions_out = tb->actions_out;
+  oa.clip_actions = rp->clip_actions;
+  oa.action_scale = rp->action_scale;
+  for (int k = 0; k < 6; k++) oa.cmd_limit[k] = rp->cmd_limit[k];
+  hipLaunchKernelGGL(mgr::k_reach_pre, dim3((sim->n + mgd::kTeams - 1) / mgd::kTeams), dim3(64),
+                     mgd::scratch_bytes(sim->host_model.num_nodes), (hipStream_t)stream,
+                     (const mgd::DynModel*)sim->d_dyn, sim->n, p, oa, (const float*)sim->views.root_states,
+                     (const float*)sim->views.dof_state, sim->views.env_props, sim->views.env_props_stride);
+  return check_launch("mg_reach_pre");
+}
+
+int mg_reach_post(mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* views, const mg_task_buffers* tb,
+                  const mg_state_views* state, void* stream) {
+  if (int rc = reach_args_ok(sim, rp, views, tb, "mg_reach_post")) return rc;
+  if (!tb->actions || !tb->obs || !tb->rew || !tb->reset || !tb->progress || !tb->timeout)
+    return fail(MG_EINVAL, "mg_reach_post: needs actions, obs, rew, reset, progress and timeout");
+  const mg_state_views& s = state ? *state : sim->views;
+  if (!s.dof_state || !s.rigid_body_states || !s.net_contact_forces)
+    return fail(MG_EINVAL, "mg_reach_post: needs dof_state, rigid_body_states and net_contact_forces");
+  const int n_envs = sim->n / rp->num_agents;
+  if (n_envs == 0) return MG_OK;
+  mgr::ReachState st{s.dof_state, s.rigid_body_states, s.net_contact_forces};
+  hipLaunchKernelGGL(mgr::k_reach_post, dim3((n_envs + mgr::kEnvs - 1) / mgr::kEnvs), dim3(64), 0,
+                     (hipStream_t)stream, *rp, *views, *tb, st, n_envs);
+  return check_launch("mg_reach_post");
+}
+
+int mg_reach_reset_idx(mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* views,
+                       const mg_task_buffers* tb, const int32_t* ids, int32_t n, void* stream) {
+  if (int rc = reach_args_ok(sim, rp, views, tb, "mg_reach_reset_idx")) return rc;
+  if (n < 0 || (n > 0 && !ids) || !tb->reset || !tb->progress)
+    return fail(MG_EINVAL, "mg_reach_reset_idx: bad arguments");
+  const int n_envs = sim->n / rp->num_agents;
+  if (n == 0 || n_envs == 0) return MG_OK;
+  mg_task_buffers t = *tb;
+  t.step_counter = tb->step_counter | (1ull << 62);   // the manual-reset stream of the counter RNG, as mg_reset_idx
+  hipLaunchKernelGGL(mgr::k_reach_reset_idx, dim3((n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, *rp,
+                     *views, t, sim->views.dof_state, ids, n, n_envs);
+  return check_launch("mg_reach_reset_idx");
+}
 
 }  // extern "C"

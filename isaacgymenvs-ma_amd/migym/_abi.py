@@ -141,6 +141,25 @@ class OscArgs(C.Structure):
                 ("out_cols", C.c_int32), ("pad_osc", C.c_int32), ("jac_in", C.c_void_p), ("mm_in", C.c_void_p)]
 
 
+class ReachParams(C.Structure):
+    """mg_reach_params: the constants of FrankaReachMA (taskdefs.reach_params)."""
+    _fields_ = [("num_agents", C.c_int32), ("num_targets", C.c_int32), ("num_obs", C.c_int32),
+                ("max_episode_length", C.c_int32), ("clip_actions", C.c_float), ("clip_obs", C.c_float),
+                ("action_scale", C.c_float), ("cmd_limit", C.c_float * 6), ("kp", C.c_float * 6),
+                ("kd", C.c_float * 6), ("kp_null", C.c_float * 7), ("kd_null", C.c_float * 7),
+                ("osc_default_dof_pos", C.c_float * 7), ("effort_limit", C.c_float * 7), ("jac_body", C.c_int32),
+                ("eef_body", C.c_int32), ("hand_body", C.c_int32), ("num_bodies", C.c_int32),
+                ("num_dofs", C.c_int32), ("default_dof_pos", C.c_float * 9), ("dof_lower", C.c_float * 9),
+                ("dof_upper", C.c_float * 9), ("dof_noise_scale", C.c_float), ("cube_xy_center", C.c_float * 2),
+                ("cube_xy_scale", C.c_float), ("cube_z_base", C.c_float), ("cube_z_range", C.c_float)]
+
+
+class ReachViews(C.Structure):
+    """mg_reach_views: the task-owned device tensors of FrankaReachMA."""
+    _fields_ = [("cube_states", C.c_void_p), ("init_cube_states", C.c_void_p), ("dof_targets", C.c_void_p),
+                ("dof_actuation", C.c_void_p)]
+
+
 def model_bytes(spec) -> np.ndarray:
     """mg_model POD for a ModelSpec (numpy structured scalar; pass .ctypes.data)."""
     return np.ascontiguousarray(_model.pack_model(spec))
@@ -202,6 +221,14 @@ EXPORTS = {
     "mg_dynamics_refresh": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mg_osc_torques": (C.c_int, [C.c_void_p, C.POINTER(OscArgs), C.c_void_p]),
     "mg_osc_args_sizeof": (C.c_size_t, []),
+    "mg_reach_params_sizeof": (C.c_size_t, []),
+    "mg_reach_views_sizeof": (C.c_size_t, []),
+    "mg_reach_pre": (C.c_int, [C.c_void_p, C.POINTER(ReachParams), C.POINTER(ReachViews), C.POINTER(TaskBuffers),
+                               C.c_void_p]),
+    "mg_reach_post": (C.c_int, [C.c_void_p, C.POINTER(ReachParams), C.POINTER(ReachViews), C.POINTER(TaskBuffers),
+                                C.POINTER(StateViews), C.c_void_p]),
+    "mg_reach_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(ReachParams), C.POINTER(ReachViews),
+                                     C.POINTER(TaskBuffers), C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 _LIB = None
@@ -224,7 +251,8 @@ def check_layout(lib):
              "mg_task_buffers_sizeof": C.sizeof(TaskBuffers), "mg_sim_params_sizeof": C.sizeof(SimParams),
              "mg_state_views_sizeof": C.sizeof(StateViews), "mg_dr_desc_sizeof": C.sizeof(DrDesc),
              "mg_dr_apply_args_sizeof": C.sizeof(DrApplyArgs), "mg_dr_noise_args_sizeof": C.sizeof(DrNoiseArgs),
-             "mg_osc_args_sizeof": C.sizeof(OscArgs)}
+             "mg_osc_args_sizeof": C.sizeof(OscArgs), "mg_reach_params_sizeof": C.sizeof(ReachParams),
+             "mg_reach_views_sizeof": C.sizeof(ReachViews)}
     for fn, py in sizes.items():
         c = getattr(lib, fn)()
         if c != py:

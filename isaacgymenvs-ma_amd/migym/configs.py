@@ -235,6 +235,24 @@ TASKS["MAAnt"] = copy.deepcopy(TASKS["Ant"])
 TASKS["MAAnt"]["name"] = "MAAnt"
 TASKS["MAAnt"]["env"].update({"numAgents": 4, "agentSpacing": 2.0})
 
+# FrankaReachMA (the fork's multi-arm reach task, cfg/task/FrankaReachMA.yaml): only the keys the task reads.  No
+# Franka asset is shipped: env.asset.modelTable names a JSON model table (tools/build_models.py franka_panda writes
+# one), or assetRoot + assetFileNameFranka a URDF.
+TASKS["FrankaReachMA"] = {
+    "name": "FrankaReachMA",
+    "env": {
+        "numEnvs": 8192, "numAgents": 2, "numTargets": -1, "episodeLength": 150,
+        "clipObservations": 5.0, "clipActions": 1.0, "startPositionNoise": 0.25, "startRotationNoise": 0.785,
+        "frankaPositionNoise": 0.0, "frankaRotationNoise": 0.0, "frankaDofNoise": 0.25, "actionScale": 1.0,
+        "controlType": "osc", "controlFrequencyInv": 1,
+        "asset": {"assetRoot": "../../assets",
+                  "assetFileNameFranka": "urdf/franka_description/robots/franka_panda_gripper.urdf"},
+    },
+    "sim": _sim(dt=0.01667, num_position_iterations=8, num_velocity_iterations=1, contact_offset=0.005,
+                rest_offset=0.0, bounce_threshold_velocity=0.2, max_depenetration_velocity=1000.0),
+    "task": {"randomize": False},
+}
+
 
 def resolve_default(default, arg):
     """``${resolve_default:d,x}`` (isaacgymenvs/__init__.py:11)."""

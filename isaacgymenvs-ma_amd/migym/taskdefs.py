@@ -22,6 +22,9 @@ TASK_INFO = {
 # observationType -> (layout id, obs size) (shadow_hand.py:108-113; layouts in csrc/hand_task.hpp)
 HAND_OBS = {"full_state": (0, 211), "full": (1, 157), "full_no_vel": (2, 77), "openai": (3, 42)}
 TASK_INFO["MAAnt"] = TASK_INFO["Ant"]   # per-agent physics/obs of the multi-agent Ant are the Ant's
+# FrankaReachMA has no fused-kernel task id and no shipped table (env.asset.modelTable names one); its obs size depends
+# on numAgents / numTargets (reach_params); z = franka_start_z (franka_reach_MA.py:415)
+TASK_INFO["FrankaReachMA"] = (None, None, 0, 6, 1.0 + 0.05 / 2 + 0.1, 8)
 
 # build-defined solver constants
 BAUMGARTE = 0.2
@@ -218,3 +221,93 @@ def task_params(task: str, cfg: dict, spec: M.ModelSpec) -> _abi.TaskParams:
         # initial_dof_pos: 0 clamped into the limits (ant.py:96-99)
         tp.initial_dof_pos[i] = a if a > 0 else (b if b < 0 else 0.0)
     return tp
+
+
+# ---- FrankaReachMA (franka_reach_MA.py)
+FRANKA_DEFAULT_DOF_POS = [0, 0.1963, 0, -2.6180, 0, 2.9416, 0.7854, 0.035, 0.035]   # franka_reach_MA.py:206-208
+FRANKA_CMD_LIMIT = [0.1, 0.1, 0.1, 0.5, 0.5, 0.5]                                  # franka_reach_MA.py:219
+REACH_HAND, REACH_EEF = "panda_hand", "panda_grip_site"
+REACH_TABLE_THICKNESS, REACH_STAND_HEIGHT, REACH_CUBE_SIZE = 0.05, 0.1, 0.050       # franka_reach_MA.py:270-282
+
+
+def reach_counts(env: dict):
+    """(numAgents, numTargets) as the reference resolves them (franka_reach_MA.py:69-72), validated"""
+    A = int(env.get("numAgents", 1))
+    T = int(env.get("numTargets", -1))
+    if T <= -1:
+        T = A
+    if A < 1 or A > 8:
+        raise ValueError(f"numAgents must be 1..8, got {A}")
+    if T < 1 or T > A:
+        # the reference's mask[env_ids, nc] indexes an A-wide mask by cube id (franka_reach_MA.py:945-948)
+        raise ValueError(f"numTargets must be 1..numAgents ({A}) or -1, got {T}")
+    return A, T
+
+
+def franka_start_poses(A: int, r: float = 0.45):
+    """_get_franka_start_poses_rots (franka_reach_MA.py:912-918): base positions (A, 2) on a circle of radius r and
+    the rotations about z (A, 4), as float32 tensors"""
+    import torch
+    rads = torch.deg2rad(torch.tensor(range(0, 359, 360 // A), dtype=torch.float))
+    pos = torch.stack([-torch.cos(rads), torch.sin(rads)], dim=-1) * r
+    zero = torch.zeros(rads.shape[-1])
+    rot = torch.stack([zero, zero, torch.sin(-rads / 2), torch.cos(-rads / 2)], dim=-1)
+    return pos[:A], rot[:A]
+
+
+def reach_spec(spec: M.ModelSpec) -> M.ModelSpec:
+    """The arm as the task configures it, on a copy (franka_reach_MA.py:259, 265-266, 309-327): arm joints in effort
+    mode (no stiffness, damping or drive), fingers position-driven (kp 5000, damping 100, effort 200), no gravity."""
+    import copy
+    spec = copy.deepcopy(spec)
+    if spec.num_dofs != 9 or not spec.fixed_base:
+        raise ValueError("FrankaReachMA needs a fixed-base 9-DOF Franka model (7 arm joints, 2 fingers)")
+    for j, n in enumerate(spec.nodes[1:]):
+        n.stiffness = 0.0
+        if j < 7:
+            n.damping, n.drive_kp = 0.0, 0.0
+        else:
+            n.damping, n.drive_kp, n.effort_limit = 100.0, 5000.0, 200.0
+    spec.gravity_off = 1
+    return spec
+
+
+def reach_params(cfg: dict, spec: M.ModelSpec) -> _abi.ReachParams:
+    """FrankaReachMA constants (franka_reach_MA.py:40-80, 205-220, 616-704), computed the way the reference's
+    expressions do: Python floats where it has floats, a float32 tensor where it has one.  ``spec``: the loaded
+    table (its effort limits are the asset's, read before the task raises the fingers' to 200)."""
+    import torch
+    env = cfg["env"]
+    A, T = reach_counts(env)
+    rp = _abi.ReachParams()
+    rp.num_agents, rp.num_targets = A, T
+    rp.num_obs = 10 + 3 * T + 3 * (A - 1)
+    rp.max_episode_length = int(env["episodeLength"])
+    rp.clip_actions = float(env.get("clipActions", math.inf))
+    rp.clip_obs = float(env.get("clipObservations", math.inf))
+    rp.action_scale = float(env.get("actionScale", 1.0))
+    kp = torch.tensor([150.0] * 6)
+    kd = 2 * torch.sqrt(kp)
+    kpn = torch.tensor([10.0] * 7)
+    kdn = 2 * torch.sqrt(kpn)
+    for k in range(6):
+        rp.cmd_limit[k] = FRANKA_CMD_LIMIT[k]
+        rp.kp[k], rp.kd[k] = float(kp[k]), float(kd[k])
+    for k in range(7):
+        rp.kp_null[k], rp.kd_null[k] = float(kpn[k]), float(kdn[k])
+        rp.osc_default_dof_pos[k] = FRANKA_DEFAULT_DOF_POS[k]
+        rp.effort_limit[k] = spec.nodes[1 + k].effort_limit
+    rp.jac_body = rp.hand_body = spec.body_index(REACH_HAND)
+    rp.eef_body = spec.body_index(REACH_EEF)
+    rp.num_bodies, rp.num_dofs = len(spec.bodies), spec.num_dofs
+    for j, n in enumerate(spec.nodes[1:10]):
+        rp.default_dof_pos[j] = FRANKA_DEFAULT_DOF_POS[j]
+        rp.dof_lower[j], rp.dof_upper[j] = n.lower, n.upper
+    rp.dof_noise_scale = float(env.get("frankaDofNoise", 0.0)) * 2.0          # franka_reach_MA.py:633
+    rp.cube_xy_center[0] = rp.cube_xy_center[1] = 0.0                          # _table_surface_pos[:2]
+    rp.cube_xy_scale = 2.0 * float(env.get("startPositionNoise", 0.0))         # franka_reach_MA.py:696
+    table_z = 1.0 + REACH_TABLE_THICKNESS / 2                                  # _table_surface_pos[2] (float64)
+    cube_heights = torch.ones(1) * REACH_CUBE_SIZE                             # states["cubeA_size"] (float32)
+    rp.cube_z_base = float(table_z + cube_heights / 2)                         # franka_reach_MA.py:693
+    rp.cube_z_range = 0.5
+    return rp

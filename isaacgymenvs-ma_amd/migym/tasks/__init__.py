@@ -2,6 +2,7 @@
 from .locomotion import Ant, Humanoid, MAAnt
 from .cartpole import Cartpole
 from .shadow_hand import ShadowHand
+from .franka_reach_ma import FrankaReachMA
 
 isaacgym_task_map = {
     "Ant": Ant,
@@ -9,4 +10,5 @@ isaacgym_task_map = {
     "Cartpole": Cartpole,
     "MAAnt": MAAnt,
     "ShadowHand": ShadowHand,
+    "FrankaReachMA": FrankaReachMA,
 }

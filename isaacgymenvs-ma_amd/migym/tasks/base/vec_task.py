@@ -260,8 +260,7 @@ class VecTask(DomainRandomizationMixin, Env):
         ev = self.launch_events   # optional (start, end) torch.cuda.Event pair around the launch (bench.py)
         if ev is not None:
             ev[0].record(torch.cuda.current_stream(self.device))
-        _abi.check(self._lib.mg_env_step(self.sim, _abi.C.byref(self.task_params), _abi.C.byref(tb), stream),
-                   self._lib)
+        self._launch_step(tb, stream)
         if ev is not None:
             ev[1].record(torch.cuda.current_stream(self.device))
         self.post_launch()
@@ -279,6 +278,12 @@ class VecTask(DomainRandomizationMixin, Env):
         if self.num_states > 0:
             self.obs_dict["states"] = self.get_state()
         return self.obs_dict, self.rew_buf.to(self.rl_device), self.reset_buf.to(self.rl_device), self.extras
+
+    def _launch_step(self, tb, stream):
+        """The device work of one control step, on ``stream``: the fused ``mg_env_step`` launch.  A task whose step
+        is not one of the fused kernels (FrankaReachMA: three launches) overrides this and nothing else of ``step``."""
+        _abi.check(self._lib.mg_env_step(self.sim, _abi.C.byref(self.task_params), _abi.C.byref(tb), stream),
+                   self._lib)
 
     def _dr_step(self, mask, pending_increment):
         """apply_randomizations as reset_idx calls it (only when some env resets: with dr_exact_trigger this

@@ -55,6 +55,9 @@ def get_rlgames_env_creator(seed, task_config, task_name, sim_device, rl_device,
         # GPU with host-side views of every tensor (migym/host_pipeline.py)
         dev_type, _, dev_id = str(sim_device).partition(":")
         host = not cfg.get("sim", {}).get("use_gpu_pipeline", True) or dev_type.lower() not in ("cuda", "gpu")
+        if host and not getattr(isaacgym_task_map[task_name], "supports_host_pipeline", True):
+            raise NotImplementedError(f"{task_name}: the CPU host pipeline is not built for this task (its task-owned "
+                                      "tensors have no host mirrors yet); use the GPU pipeline")
         if host:
             if dev_type.lower() not in ("cuda", "gpu"):
                 print("GPU Pipeline can only be used with GPU simulation. Forcing CPU Pipeline.")

@@ -242,4 +242,11 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    import sys
+    if sys.argv[1:2] == ["franka_panda"]:
+        # the Franka table alone (FrankaReachMA's env.asset.modelTable): `build_models.py franka_panda [OUT.json]`
+        path = sys.argv[2] if len(sys.argv) > 2 else FRANKA_JSON
+        franka_panda().to_json(path)
+        print("wrote", path)
+    else:
+        main()
