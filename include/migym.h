@@ -653,6 +653,67 @@ int mg_reach_post(mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* 
 int mg_reach_reset_idx(mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* views,
                        const mg_task_buffers* tb, const int32_t* ids, int32_t n, void* stream);
 
+/* ---- Anymal (anymal.py): the PD-driven quadruped as three launches per control step -- mg_anymal_pre,
+ * mg_sim_simulate x controlFrequencyInv, mg_anymal_post -- all asynchronous on the caller's stream, no host
+ * synchronisation.  One free-base 12-DOF articulation per env, every DOF on a position drive (the model's drive_kp /
+ * damping / effort_limit); the sim must have dof_targets, dof_force and net_contact_forces bound.  New structs only:
+ * the step kernels and their argument structs are untouched, and mg_task_buffers is reused for the VecTask buffers. */
+#define MG_ANYMAL_DOFS 12
+#define MG_ANYMAL_OBS 48
+#define MG_ANYMAL_NOISE_COLS 27
+typedef struct mg_anymal_params {
+  float lin_vel_scale, ang_vel_scale, dof_pos_scale, dof_vel_scale;   /* learn.*Scale (anymal.py:49-52) */
+  float action_scale;                 /* control.actionScale */
+  /* learn.*RewardScale * dt, the product taken in double on the host (anymal.py:99-100) and rounded to fp32 */
+  float rew_lin_vel_xy, rew_ang_vel_z, rew_torque;
+  float default_dof_pos[MG_ANYMAL_DOFS];   /* defaultJointAngles in DOF order */
+  float base_init_state[13];          /* pos 3 | rot 4 (xyzw) | vLinear 3 | vAngular 3 */
+  /* randomCommandVelocityRanges linear_x, linear_y, yaw: a draw is command_span * u + command_lo with
+   * command_span = hi - lo subtracted in double on the host (torch_rand_float's Python floats) */
+  float command_lo[3], command_span[3];
+  int32_t base_body;                  /* net_contact_forces row of the base */
+  int32_t knee_body[4];               /* ... of the four THIGH bodies */
+  int32_t num_bodies;                 /* rigid-body rows per env */
+  float clip_actions, clip_obs;
+  int32_t max_episode_length;         /* int(episodeLength_s / dt + 0.5) */
+} mg_anymal_params;
+
+/* task-owned device tensors */
+typedef struct mg_anymal_views {
+  float* commands;                    /* (N, 3) [x, y, yaw] */
+  float* dof_targets;                 /* (N*12): the buffer the sim has bound as dof_targets */
+} mg_anymal_views;
+size_t mg_anymal_params_sizeof(void);
+size_t mg_anymal_views_sizeof(void);
+
+/* mg_task_buffers fields the Anymal entry points use: actions (N, 12), actions_out, obs (N, 48), obs_clamped, rew,
+ * reset, progress, timeout, noise, seed, step_counter, env_offset, out_pack.  noise: (N, 27) U(0,1) per env, in the
+ * reference's draw order [positions_offset 12 | velocities 12 | command x | y | yaw] (anymal.py:283-301); NULL = the
+ * counter RNG keyed by (seed, env_offset + env, step_counter, column). */
+
+/* pre_physics_step (anymal.py:226-229), one launch: actions_out = clamp(actions, +-clip_actions), dof_targets =
+ * action_scale * actions_out + default_dof_pos (a product, then a sum: no FMA). */
+int mg_anymal_pre(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* views, const mg_task_buffers* tb,
+                  void* stream);
+
+/* post_physics_step + the VecTask.step tail (anymal.py:231-304, 311-386), one launch, per env: progress += 1; an env
+ * with reset != 0 is reset (dof_pos = default * U(0.5, 1.5), dof_vel = U(-0.1, 0.1), root row = base_init_state, three
+ * new commands, progress = 0), visible at once; observations [base lin vel 3 | base ang vel 3 | projected gravity 3 |
+ * scaled commands 3 | dof pos 12 | dof vel 12 | actions 12]; compute_anymal_reward (clipped at 0; reset on a base or
+ * THIGH net contact force norm > 1 or progress >= max_episode_length - 1) with dof_force and net_contact_forces as
+ * simulate left them; timeout, obs clamp, out_pack.
+ * state: NULL = the sim's bound views; else its root_states, dof_state, dof_force and net_contact_forces are taken as
+ * the post-simulate state (physics-free replay; root_states and dof_state are written by a reset). */
+int mg_anymal_post(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* views, const mg_task_buffers* tb,
+                   const mg_state_views* state, void* stream);
+
+/* reset_idx(env_ids) now (anymal.py:278-304): the n listed envs get the reset of mg_anymal_post and, as the
+ * reference's reset_idx leaves them, progress = 0 and reset = 1; a repeated id is harmless, an id outside 0..N-1 is
+ * skipped.  Noise: tb->noise rows by env, or the counter RNG on the manual-reset stream (step_counter | 2^62), as
+ * mg_reset_idx. */
+int mg_anymal_reset_idx(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* views,
+                        const mg_task_buffers* tb, const int32_t* ids, int32_t n, void* stream);
+
 /* Measurement aid (no reference counterpart; bench.py's roofline.kernel_ms): the device-side duration of the
  * fused step kernel, from the first wave's start to the last wave's end on the GPU's constant wall clock
  * (wall_clock64, hipDeviceAttributeWallClockRate), so that no launch, queue or event-packet overhead is in it.
@@ -676,6 +737,9 @@ int mg_work_order(mg_sim* sim, int32_t* order, uint8_t* cost, int32_t cap, int32
  * team_lanes = lanes per actor (T), compact = 1 for the 12-waves-per-CU compact team layout, 0 for the classic one
  * (MIGYM_LAYOUT = auto | compact | classic, read at mg_sim_create). */
 int mg_sim_kernel_layout(mg_sim* sim, int32_t* team_lanes, int32_t* compact);
+/* The same rule without a sim or a device: team_lanes = lanes per actor of the first instance that fits `model` at
+ * `max_contacts` contacts (mgi::team_size, csrc/dispatch.hpp), 0 if none fits.  Host code only. */
+int mg_model_team_lanes(const mg_model* model, int32_t max_contacts, int32_t* team_lanes);
 
 #ifdef __cplusplus
 }

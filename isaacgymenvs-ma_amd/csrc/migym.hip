@@ -10,6 +10,7 @@
 
 #include "dispatch.hpp"
 #include "dynamics_tensors.hpp"
+#include "anymal_task.hpp"  // as reach_task.hpp: restores FMA contraction at its end
 #include "reach_task.hpp"   // before hand_task.hpp: that header leaves FMA contraction off for the rest of this file
 #include "hand_task.hpp"
 #include "task.hpp"
@@ -892,6 +893,12 @@ int mg_sim_kernel_layout(mg_sim* sim, int32_t* team_lanes, int32_t* compact) {
   return mgi::dispatch<mgi::InstanceOf>(sim->host_model, sim->params.max_contacts, sim->layout_n, team_lanes, compact);
 }
 
+int mg_model_team_lanes(const mg_model* model, int32_t max_contacts, int32_t* team_lanes) {
+  if (!model || !team_lanes) return fail(MG_EINVAL, "mg_model_team_lanes: bad arguments");
+  *team_lanes = mgi::team_size(*model, max_contacts);
+  return MG_OK;
+}
+
 int mg_set_indexed(mg_sim* sim, int32_t which, const float* src, const int32_t* idx, int32_t n, void* stream) {
   if (!sim || !sim->bound || !src || (n > 0 && !idx)) return fail(MG_EINVAL, "mg_set_indexed: bad arguments");
   if (n == 0) return MG_OK;
@@ -1362,6 +1369,71 @@ int mg_reach_reset_idx(mg_sim* sim, const mg_reach_params* rp, const mg_reach_vi
   hipLaunchKernelGGL(mgr::k_reach_reset_idx, dim3((n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, *rp,
                      *views, t, sim->views.dof_state, ids, n, n_envs);
   return check_launch("mg_reach_reset_idx");
+}
+
+// ---- Anymal: the task layer around mg_sim_simulate (anymal_task.hpp)
+size_t mg_anymal_params_sizeof(void) { return sizeof(mg_anymal_params); }
+size_t mg_anymal_views_sizeof(void) { return sizeof(mg_anymal_views); }
+
+// the shared argument check: a bound free-base 12-DOF sim whose body count matches the task constants
+static int anymal_args_ok(const mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* v,
+                          const mg_task_buffers* tb, const char* who) {
+  if (!sim || !ap || !v || !tb) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
+  if (!sim->bound) return fail(MG_EINVAL, std::string(who) + ": sim not bound");
+  const mg_model& m = sim->host_model;
+  if (m.fixed_base || m.obj_type || m.num_nodes - 1 != MG_ANYMAL_DOFS)
+    return fail(MG_EINVAL, std::string(who) + ": needs a free-base model of 12 DOFs without a free object");
+  if (ap->num_bodies != m.num_bodies) return fail(MG_EINVAL, std::string(who) + ": num_bodies does not match the sim's model");
+  if (ap->base_body < 0 || ap->base_body >= m.num_bodies)
+    return fail(MG_EINVAL, std::string(who) + ": base_body out of range");
+  for (int k = 0; k < 4; k++)
+    if (ap->knee_body[k] < 0 || ap->knee_body[k] >= m.num_bodies)
+      return fail(MG_EINVAL, std::string(who) + ": knee_body out of range");
+  if (!v->commands || !v->dof_targets) return fail(MG_EINVAL, std::string(who) + ": needs commands and dof_targets");
+  return MG_OK;
+}
+
+int mg_anymal_pre(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* views, const mg_task_buffers* tb,
+                  void* stream) {
+  if (int rc = anymal_args_ok(sim, ap, views, tb, "mg_anymal_pre")) return rc;
+  if (!tb->actions) return fail(MG_EINVAL, "mg_anymal_pre: needs actions");
+  if (sim->views.dof_targets != views->dof_targets)
+    return fail(MG_EINVAL, "mg_anymal_pre: views.dof_targets is not the buffer the sim has bound as dof_targets");
+  if (sim->n == 0) return MG_OK;
+  const long long total = (long long)sim->n * MG_ANYMAL_DOFS;
+  hipLaunchKernelGGL(mga::k_anymal_pre, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *ap,
+                     tb->actions, tb->actions_out, views->dof_targets, total);
+  return check_launch("mg_anymal_pre");
+}
+
+int mg_anymal_post(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* views, const mg_task_buffers* tb,
+                   const mg_state_views* state, void* stream) {
+  if (int rc = anymal_args_ok(sim, ap, views, tb, "mg_anymal_post")) return rc;
+  if (!tb->actions || !tb->obs || !tb->rew || !tb->reset || !tb->progress || !tb->timeout)
+    return fail(MG_EINVAL, "mg_anymal_post: needs actions, obs, rew, reset, progress and timeout");
+  const mg_state_views& s = state ? *state : sim->views;
+  if (!s.root_states || !s.dof_state || !s.dof_force || !s.net_contact_forces)
+    return fail(MG_EINVAL, "mg_anymal_post: needs root_states, dof_state, dof_force and net_contact_forces");
+  if (sim->n == 0) return MG_OK;
+  mga::AnymalState st{s.root_states, s.dof_state, s.dof_force, s.net_contact_forces};
+  hipLaunchKernelGGL(mga::k_anymal_post, dim3((sim->n + mga::kEnvs - 1) / mga::kEnvs), dim3(64), 0,
+                     (hipStream_t)stream, *ap, *views, *tb, st, sim->n);
+  return check_launch("mg_anymal_post");
+}
+
+int mg_anymal_reset_idx(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* views,
+                        const mg_task_buffers* tb, const int32_t* ids, int32_t n, void* stream) {
+  if (int rc = anymal_args_ok(sim, ap, views, tb, "mg_anymal_reset_idx")) return rc;
+  if (n < 0 || (n > 0 && !ids) || !tb->reset || !tb->progress || !sim->views.root_states || !sim->views.dof_state)
+    return fail(MG_EINVAL, "mg_anymal_reset_idx: bad arguments");
+  if (n == 0 || sim->n == 0) return MG_OK;
+  mg_task_buffers t = *tb;
+  t.step_counter = tb->step_counter | (1ull << 62);   // the manual-reset stream of the counter RNG, as mg_reset_idx
+  mga::AnymalState st{sim->views.root_states, sim->views.dof_state, sim->views.dof_force,
+                      sim->views.net_contact_forces};
+  hipLaunchKernelGGL(mga::k_anymal_reset_idx, dim3((n + mga::kEnvs - 1) / mga::kEnvs), dim3(64), 0,
+                     (hipStream_t)stream, *ap, *views, t, st, ids, n, sim->n);
+  return check_launch("mg_anymal_reset_idx");
 }
 
 }  // extern "C"

@@ -1,1 +1,1 @@
-from migym.tasks import isaacgym_task_map, Ant, Humanoid, Cartpole, FrankaReachMA  # noqa: F401
+from migym.tasks import isaacgym_task_map, Ant, Humanoid, Cartpole, FrankaReachMA, Anymal  # noqa: F401

@@ -160,6 +160,25 @@ class ReachViews(C.Structure):
                 ("dof_actuation", C.c_void_p)]
 
 
+MG_ANYMAL_DOFS, MG_ANYMAL_OBS, MG_ANYMAL_NOISE_COLS = 12, 48, 27
+
+
+class AnymalParams(C.Structure):
+    """mg_anymal_params: the constants of Anymal (taskdefs.anymal_params)."""
+    _fields_ = [("lin_vel_scale", C.c_float), ("ang_vel_scale", C.c_float), ("dof_pos_scale", C.c_float),
+                ("dof_vel_scale", C.c_float), ("action_scale", C.c_float), ("rew_lin_vel_xy", C.c_float),
+                ("rew_ang_vel_z", C.c_float), ("rew_torque", C.c_float),
+                ("default_dof_pos", C.c_float * MG_ANYMAL_DOFS), ("base_init_state", C.c_float * 13),
+                ("command_lo", C.c_float * 3), ("command_span", C.c_float * 3), ("base_body", C.c_int32),
+                ("knee_body", C.c_int32 * 4), ("num_bodies", C.c_int32), ("clip_actions", C.c_float),
+                ("clip_obs", C.c_float), ("max_episode_length", C.c_int32)]
+
+
+class AnymalViews(C.Structure):
+    """mg_anymal_views: the task-owned device tensors of Anymal."""
+    _fields_ = [("commands", C.c_void_p), ("dof_targets", C.c_void_p)]
+
+
 def model_bytes(spec) -> np.ndarray:
     """mg_model POD for a ModelSpec (numpy structured scalar; pass .ctypes.data)."""
     return np.ascontiguousarray(_model.pack_model(spec))
@@ -205,6 +224,7 @@ EXPORTS = {
     "mg_work_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int32)]),
     "mg_sim_kernel_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mg_model_team_lanes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]),
     "mg_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(TaskParams), C.POINTER(TaskBuffers), C.c_void_p, C.c_int32,
                                C.c_void_p]),
     "mg_env_step_replay": (C.c_int, [C.c_void_p, C.POINTER(TaskParams), C.POINTER(TaskBuffers), C.POINTER(Replay),
@@ -229,6 +249,14 @@ EXPORTS = {
                                 C.POINTER(StateViews), C.c_void_p]),
     "mg_reach_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(ReachParams), C.POINTER(ReachViews),
                                      C.POINTER(TaskBuffers), C.c_void_p, C.c_int32, C.c_void_p]),
+    "mg_anymal_params_sizeof": (C.c_size_t, []),
+    "mg_anymal_views_sizeof": (C.c_size_t, []),
+    "mg_anymal_pre": (C.c_int, [C.c_void_p, C.POINTER(AnymalParams), C.POINTER(AnymalViews), C.POINTER(TaskBuffers),
+                                C.c_void_p]),
+    "mg_anymal_post": (C.c_int, [C.c_void_p, C.POINTER(AnymalParams), C.POINTER(AnymalViews), C.POINTER(TaskBuffers),
+                                 C.POINTER(StateViews), C.c_void_p]),
+    "mg_anymal_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(AnymalParams), C.POINTER(AnymalViews),
+                                      C.POINTER(TaskBuffers), C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 _LIB = None
@@ -252,7 +280,8 @@ def check_layout(lib):
              "mg_state_views_sizeof": C.sizeof(StateViews), "mg_dr_desc_sizeof": C.sizeof(DrDesc),
              "mg_dr_apply_args_sizeof": C.sizeof(DrApplyArgs), "mg_dr_noise_args_sizeof": C.sizeof(DrNoiseArgs),
              "mg_osc_args_sizeof": C.sizeof(OscArgs), "mg_reach_params_sizeof": C.sizeof(ReachParams),
-             "mg_reach_views_sizeof": C.sizeof(ReachViews)}
+             "mg_reach_views_sizeof": C.sizeof(ReachViews), "mg_anymal_params_sizeof": C.sizeof(AnymalParams),
+             "mg_anymal_views_sizeof": C.sizeof(AnymalViews)}
     for fn, py in sizes.items():
         c = getattr(lib, fn)()
         if c != py:

@@ -253,6 +253,32 @@ TASKS["FrankaReachMA"] = {
     "task": {"randomize": False},
 }
 
+# Anymal (cfg/task/Anymal.yaml): only the keys the task reads.  No ANYmal asset is shipped: env.asset.modelTable names
+# a JSON model table (tools/build_models.py anymal_c writes one), or assetRoot + assetFileName the URDF.
+TASKS["Anymal"] = {
+    "name": "Anymal",
+    "env": {
+        "numEnvs": 4096, "envSpacing": 4.0, "clipObservations": 5.0, "clipActions": 1.0,
+        "plane": dict(_LOCO_PLANE),
+        "baseInitState": {"pos": [0.0, 0.0, 0.62], "rot": [0.0, 0.0, 0.0, 1.0], "vLinear": [0.0, 0.0, 0.0],
+                          "vAngular": [0.0, 0.0, 0.0]},
+        "randomCommandVelocityRanges": {"linear_x": [-2.0, 2.0], "linear_y": [-1.0, 1.0], "yaw": [-1.0, 1.0]},
+        "control": {"stiffness": 85.0, "damping": 2.0, "actionScale": 0.5, "controlFrequencyInv": 1},
+        "defaultJointAngles": {"LF_HAA": 0.03, "LH_HAA": 0.03, "RF_HAA": -0.03, "RH_HAA": -0.03,
+                               "LF_HFE": 0.4, "LH_HFE": -0.4, "RF_HFE": 0.4, "RH_HFE": -0.4,
+                               "LF_KFE": -0.8, "LH_KFE": 0.8, "RF_KFE": -0.8, "RH_KFE": 0.8},
+        "urdfAsset": {"collapseFixedJoints": True, "fixBaseLink": False, "defaultDofDriveMode": 4},
+        "learn": {"linearVelocityXYRewardScale": 1.0, "angularVelocityZRewardScale": 0.5,
+                  "torqueRewardScale": -0.000025, "linearVelocityScale": 2.0, "angularVelocityScale": 0.25,
+                  "dofPositionScale": 1.0, "dofVelocityScale": 0.05, "episodeLength_s": 50},
+        "asset": {"assetRoot": "../../assets", "assetFileName": "urdf/anymal_c/urdf/anymal.urdf"},
+        "enableCameraSensors": False,
+    },
+    "sim": _sim(dt=0.02, num_position_iterations=4, num_velocity_iterations=1, contact_offset=0.02, rest_offset=0.0,
+                bounce_threshold_velocity=0.2, max_depenetration_velocity=100.0, contact_collection=1),
+    "task": {"randomize": False},
+}
+
 
 def resolve_default(default, arg):
     """``${resolve_default:d,x}`` (isaacgymenvs/__init__.py:11)."""

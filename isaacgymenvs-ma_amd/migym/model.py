@@ -667,8 +667,16 @@ def self_collision_pairs(spec: ModelSpec):
 
 
 # ---------------------------------------------------------------------------------------------
-def load_urdf(path, name=None, fix_base=True) -> ModelSpec:
-    """URDF loader (prismatic / revolute / continuous / fixed joints)."""
+def load_urdf(path, name=None, fix_base=True, *, collapse_fixed=False, replace_cylinder_with_capsule=False,
+              effort_limits=False) -> ModelSpec:
+    """URDF loader (prismatic / revolute / continuous / fixed joints).
+
+    ``collapse_fixed`` (gym ``AssetOptions.collapse_fixed_joints``, anymal.py:172): a link joined to its parent by a
+    fixed joint gets no rigid-body row; its geoms take the parent body's index, and its inertial accumulates into
+    that body's mass and COM (the node tables are the same either way: a fixed joint never made a node).
+    ``replace_cylinder_with_capsule`` (anymal.py:173): a cylinder (r, L) becomes a capsule of the same radius and
+    axis with segment half-length L/2 -- PhysX's capsule convention, build-defined here.
+    ``effort_limits``: ``Node.effort_limit`` is read from ``<limit effort>``."""
     root = ET.parse(path).getroot()
     links = {l.get("name"): l for l in root.findall("link")}
     joints = root.findall("joint")
@@ -693,7 +701,9 @@ def load_urdf(path, name=None, fix_base=True) -> ModelSpec:
         rpy = _floats(o.get("rpy", "0 0 0"))
         return Xform(xyz, quat_from_rpy(*rpy))
 
-    def link_content(link, node_idx, body_idx, T: Xform):
+    def link_content(link, node_idx, body_idx, T: Xform, T_b: Xform):
+        # T: the link frame in its node's frame; T_b: the link frame in its rigid body's frame (identity unless the
+        # link is collapsed into an ancestor)
         col_boxes = []
         for c in link.findall("collision"):
             Xc = origin(c)
@@ -708,7 +718,8 @@ def load_urdf(path, name=None, fix_base=True) -> ModelSpec:
             elif sph is not None:
                 g = (GT_SPHERE, [float(sph.get("radius")), 0, 0])
             elif cyl is not None:
-                g = (GT_CYLINDER, [float(cyl.get("radius")), 0.5 * float(cyl.get("length")), 0])
+                g = (GT_CAPSULE if replace_cylinder_with_capsule else GT_CYLINDER,
+                     [float(cyl.get("radius")), 0.5 * float(cyl.get("length")), 0])
             else:
                 continue
             Xn = T.compose(Xc)
@@ -743,12 +754,14 @@ def load_urdf(path, name=None, fix_base=True) -> ModelSpec:
         Xn = T.compose(Xi)
         R = qmat(Xn.rot)
         accs.setdefault(node_idx, _MassAccum()).add(m, Xn.pos, R @ I @ R.T)
-        Rb = qmat(Xi.rot)
-        baccs.setdefault(body_idx, _MassAccum()).add(m, Xi.pos, Rb @ I @ Rb.T)
+        Xb = T_b.compose(Xi)
+        Rb = qmat(Xb.rot)
+        baccs.setdefault(body_idx, _MassAccum()).add(m, Xb.pos, Rb @ I @ Rb.T)
 
-    def visit(link_name, parent_node, T_parent: Xform, parent_body):
+    def visit(link_name, parent_node, T_parent: Xform, parent_body, T_b_parent: Xform = None):
         body_idx = len(bodies)
         link = links[link_name]
+        T_b = Xform()
         if parent_node < 0:
             nodes.append(Node(name=link_name, parent=-1, jtype=JT_FIXED if fix_base else JT_FREE, t=[0, 0, 0],
                               r0=[0, 0, 0, 1], axis=[0, 0, 1], body=body_idx))
@@ -759,6 +772,9 @@ def load_urdf(path, name=None, fix_base=True) -> ModelSpec:
             Xj = T_parent.compose(origin(j))
             if jt == "fixed":
                 node_idx, T = parent_node, Xj
+                if collapse_fixed:
+                    body_idx = parent_body
+                    T_b = (T_b_parent or Xform()).compose(origin(j))
             else:
                 ax = j.find("axis")
                 axis = np.array(_floats(ax.get("xyz"))) if ax is not None else np.array([1.0, 0, 0])
@@ -773,13 +789,16 @@ def load_urdf(path, name=None, fix_base=True) -> ModelSpec:
                                   axis=[float(v) for v in axis], body=body_idx,
                                   damping=float(dyn.get("damping", "0")) if dyn is not None else 0.0,
                                   lower=lo, upper=hi, limited=int(jt in ("prismatic", "revolute"))))
+                if effort_limits and lim is not None:
+                    nodes[-1].effort_limit = float(lim.get("effort", "0"))
                 dof_names.append(j.get("name"))
                 node_idx, T = len(nodes) - 1, Xform()
-        bodies.append(Body(name=link_name, node=node_idx, pos=[float(v) for v in T.pos],
-                           quat=[float(v) for v in T.rot], parent_body=parent_body))
-        link_content(link, node_idx, body_idx, T)
+        if body_idx == len(bodies):
+            bodies.append(Body(name=link_name, node=node_idx, pos=[float(v) for v in T.pos],
+                               quat=[float(v) for v in T.rot], parent_body=parent_body))
+        link_content(link, node_idx, body_idx, T, T_b)
         for j in children.get(link_name, []):
-            visit(j.find("child").get("link"), node_idx, T, body_idx)
+            visit(j.find("child").get("link"), node_idx, T, body_idx, T_b)
 
     visit(root_link, -1, Xform(), -1)
     for i, n in enumerate(nodes):

@@ -25,6 +25,9 @@ TASK_INFO["MAAnt"] = TASK_INFO["Ant"]   # per-agent physics/obs of the multi-age
 # FrankaReachMA has no fused-kernel task id and no shipped table (env.asset.modelTable names one); its obs size depends
 # on numAgents / numTargets (reach_params); z = franka_start_z (franka_reach_MA.py:415)
 TASK_INFO["FrankaReachMA"] = (None, None, 0, 6, 1.0 + 0.05 / 2 + 0.1, 8)
+# Anymal: no fused-kernel task id and no shipped table either; z = baseInitState.pos[2]; 48 contacts put the 13-node
+# model on the (32, 32, 48, 48, 192) instance (37 geoms need MG >= 48 anyway)
+TASK_INFO["Anymal"] = (None, None, 48, 12, 0.62, 48)
 
 # build-defined solver constants
 BAUMGARTE = 0.2
@@ -311,3 +314,63 @@ def reach_params(cfg: dict, spec: M.ModelSpec) -> _abi.ReachParams:
     rp.cube_z_base = float(table_z + cube_heights / 2)                         # franka_reach_MA.py:693
     rp.cube_z_range = 0.5
     return rp
+
+
+# ---- Anymal (anymal.py)
+ANYMAL_BASE, ANYMAL_KNEE, ANYMAL_FOOT = "base", "THIGH", "SHANK"   # anymal.py:192-197, 224 (collapsed fixed joints)
+
+
+def anymal_spec(spec: M.ModelSpec, cfg: dict) -> M.ModelSpec:
+    """The quadruped as the task configures it, on a copy (anymal.py:170-180, 199-203): every DOF on a position drive
+    with env.control's stiffness and damping (the effort limits stay the asset's), no link angular damping."""
+    import copy
+    spec = copy.deepcopy(spec)
+    if spec.num_dofs != _abi.MG_ANYMAL_DOFS or spec.fixed_base:
+        raise ValueError("Anymal needs a free-base 12-DOF model")
+    ctl = cfg["env"]["control"]
+    for n in spec.nodes[1:]:
+        n.stiffness = 0.0
+        n.drive_kp, n.damping = float(ctl["stiffness"]), float(ctl["damping"])
+    spec.angular_damping = 0.0
+    return spec
+
+
+def anymal_params(cfg: dict, spec: M.ModelSpec) -> _abi.AnymalParams:
+    """Anymal constants (anymal.py:46-100, 132-143, 192-224), computed where the reference computes them: products and
+    differences of Python floats in double, then rounded to fp32 once."""
+    env = cfg["env"]
+    learn, ctl = env["learn"], env["control"]
+    import numpy as np
+    dt = float(np.float32(cfg["sim"]["dt"]))   # self.dt = self.sim_params.dt: gymapi.SimParams.dt is a C float
+    ap = _abi.AnymalParams()
+    ap.lin_vel_scale, ap.ang_vel_scale = float(learn["linearVelocityScale"]), float(learn["angularVelocityScale"])
+    ap.dof_pos_scale, ap.dof_vel_scale = float(learn["dofPositionScale"]), float(learn["dofVelocityScale"])
+    ap.action_scale = float(ctl["actionScale"])
+    ap.rew_lin_vel_xy = float(learn["linearVelocityXYRewardScale"]) * dt      # anymal.py:99-100
+    ap.rew_ang_vel_z = float(learn["angularVelocityZRewardScale"]) * dt
+    ap.rew_torque = float(learn["torqueRewardScale"]) * dt
+    angles = env["defaultJointAngles"]
+    for j, name in enumerate(spec.dof_names):
+        ap.default_dof_pos[j] = float(angles[name])
+    b = env["baseInitState"]
+    state = list(b["pos"]) + list(b["rot"]) + list(b["vLinear"]) + list(b["vAngular"])
+    if len(state) != 13:
+        raise ValueError("baseInitState must hold pos 3, rot 4, vLinear 3, vAngular 3")
+    for c, x in enumerate(state):
+        ap.base_init_state[c] = float(x)
+    rng = env["randomCommandVelocityRanges"]
+    for c, key in enumerate(("linear_x", "linear_y", "yaw")):
+        lo, hi = float(rng[key][0]), float(rng[key][1])
+        ap.command_lo[c], ap.command_span[c] = lo, hi - lo
+    names = [x.name for x in spec.bodies]
+    knees = [i for i, s in enumerate(names) if ANYMAL_KNEE in s]
+    if len(knees) != 4 or ANYMAL_BASE not in names:
+        raise ValueError("Anymal needs a body named 'base' and four THIGH bodies")
+    ap.base_body = names.index(ANYMAL_BASE)
+    for k, i in enumerate(knees):
+        ap.knee_body[k] = i
+    ap.num_bodies = len(spec.bodies)
+    ap.clip_actions = float(env.get("clipActions", math.inf))
+    ap.clip_obs = float(env.get("clipObservations", math.inf))
+    ap.max_episode_length = int(float(learn["episodeLength_s"]) / dt + 0.5)   # anymal.py:95
+    return ap

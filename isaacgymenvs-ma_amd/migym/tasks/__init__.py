@@ -3,6 +3,7 @@ from .locomotion import Ant, Humanoid, MAAnt
 from .cartpole import Cartpole
 from .shadow_hand import ShadowHand
 from .franka_reach_ma import FrankaReachMA
+from .anymal import Anymal
 
 isaacgym_task_map = {
     "Ant": Ant,
@@ -11,4 +12,5 @@ isaacgym_task_map = {
     "MAAnt": MAAnt,
     "ShadowHand": ShadowHand,
     "FrankaReachMA": FrankaReachMA,
+    "Anymal": Anymal,
 }

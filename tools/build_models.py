@@ -29,6 +29,11 @@ them from migym/assets/*.json.
             Isaac Gym derives the masses from the collision meshes at its default density; the fixture takes
             each link's mass, COM and inertia from the convex hull of its collision mesh at 1000 kg/m^3
             (hull_mass_properties), which stands in for whatever PhysX cooks.
+  Anymal    assets/urdf/anymal_c/urdf/anymal.urdf (anymal.py:166-183: collapse_fixed_joints,
+            replace_cylinder_with_capsule, free base, angular_damping 0).  A TEST FIXTURE, written to
+            tests/golden/anymal_c.json and not shipped under migym/assets: 13 bodies (base, then
+            {LF,RF,LH,RH}_{HIP,THIGH,SHANK}), 12 DOFs, 37 primitive geoms, the URDF's inertials (52.13 kg) and its
+            effort limits (80 N m); the task sets the drive gains (env.control).
 """
 import json
 import os
@@ -165,6 +170,19 @@ def franka_panda():
     return spec
 
 
+ANYMAL_URDF = "assets/urdf/anymal_c/urdf/anymal.urdf"
+ANYMAL_JSON = os.path.join(HERE, "..", "tests", "golden", "anymal_c.json")
+
+
+def anymal_c():
+    """ANYmal C as the reference's Anymal task loads it (anymal.py:170-180): fixed joints collapsed, cylinders as
+    capsules, the URDF's effort limits per DOF node, no link angular damping."""
+    spec = M.load_urdf(os.path.join(REF, ANYMAL_URDF), "anymal_c", fix_base=False, collapse_fixed=True,
+                       replace_cylinder_with_capsule=True, effort_limits=True)
+    spec.angular_damping = 0.0      # anymal.py:177
+    return spec
+
+
 HAND_FINGERTIPS = ["robot0:ffdistal", "robot0:mfdistal", "robot0:rfdistal", "robot0:lfdistal", "robot0:thdistal"]
 HAND_TENDONS = ["robot0:T_FFJ1c", "robot0:T_MFJ1c", "robot0:T_RFJ1c", "robot0:T_LFJ1c"]
 
@@ -236,7 +254,9 @@ def main():
     print("hand objects:", {k: (v["type"], v["size"], round(v["mass"], 5)) for k, v in objs.items()})
     fr = franka_panda()
     fr.to_json(FRANKA_JSON)
-    for s in (ant, hum, cp, sh, fr):
+    an = anymal_c()
+    an.to_json(ANYMAL_JSON)
+    for s in (ant, hum, cp, sh, fr, an):
         print(f"{s.name}: nodes={len(s.nodes)} dofs={s.num_dofs} bodies={len(s.bodies)} geoms={len(s.geoms)} "
               f"pairs={len(s.pairs)} mass={s.total_mass():.4f} sensors={s.sensors}")
 
@@ -247,6 +267,11 @@ if __name__ == "__main__":
         # the Franka table alone (FrankaReachMA's env.asset.modelTable): `build_models.py franka_panda [OUT.json]`
         path = sys.argv[2] if len(sys.argv) > 2 else FRANKA_JSON
         franka_panda().to_json(path)
+        print("wrote", path)
+    elif sys.argv[1:2] == ["anymal_c"]:
+        # the Anymal table alone (Anymal's env.asset.modelTable): `build_models.py anymal_c [OUT.json]`
+        path = sys.argv[2] if len(sys.argv) > 2 else ANYMAL_JSON
+        anymal_c().to_json(path)
         print("wrote", path)
     else:
         main()
