@@ -714,6 +714,48 @@ int mg_anymal_post(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_view
 int mg_anymal_reset_idx(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* views,
                         const mg_task_buffers* tb, const int32_t* ids, int32_t n, void* stream);
 
+/* ---- Rendering (VecTask.render under virtual_screen_capture, tasks/base/vec_task.py render): a pinhole ray caster
+ * over the envs' collision geometry, two launches on the caller's stream, no host synchronisation.  The image shows
+ * the model's geoms, the hand tasks' free object and goal, the caller's extra boxes and the ground plane z = 0; visual
+ * meshes, textures and shadows are not drawn.  Additive: no existing struct or export changes.
+ *   camera     f = normalize(target - eye), r = normalize(f x (0,0,1)), u = r x f;
+ *              eye = anchor + eye_offset, target = anchor + target_offset, anchor = the root position of the env's
+ *              actor 0 when follow != 0, else the origin
+ *   pixel      (row i, column j): x = (2 (j + 0.5) / W - 1) tan(fov_y / 2) W / H, y = (1 - 2 (i + 0.5) / H) tan(fov_y / 2),
+ *              d = normalize(f + x r + y u); the nearest hit with t > 1e-4 wins, a tie goes to the lower primitive id
+ *   primitives of an env, in id order: the geoms 0..nG-1 of each actor a = 0..A-1; the free object and the goal (root
+ *              rows 1 and 2 of the env, shaped by obj_type / obj_size) when obj_type != 0; the num_boxes extra boxes;
+ *              the ground plane, last.  P = A nG + (obj_type ? 2 : 0) + num_boxes + 1 <= 512 (else MG_ECAPACITY)
+ *   shading    c = base (0.35 + 0.65 max(0, n . l)), l = normalize(0.3, 0.2, 1), n the outward world normal; base = an
+ *              8-entry palette indexed by geom_body % 8, fixed colours for the object, the goal and the extra boxes, a
+ *              two-grey 1 m checker ((floor(x) + floor(y)) & 1) on the ground, one sky colour;
+ *              uint8 = clamp(floor(255 c + 0.5), 0, 255)
+ * An env id outside 0..N-1 in the device list env_ids cannot be reported (nothing synchronises): its image is sky,
+ * depth +inf, ids -1.  migym/render.py checks ids it is given as a host list. */
+typedef struct mg_render_args {
+  int32_t width, height;       /* 1..16384 each */
+  float fov_y;                 /* vertical field of view, radians, in (0, pi) */
+  float eye_offset[3];
+  float target_offset[3];
+  int32_t follow;
+  const int32_t* env_ids;      /* (n_sel) device, or NULL = the first n_sel envs */
+  int32_t n_sel;               /* >= 1 */
+  int32_t num_boxes;           /* K >= 0 */
+  const float* boxes;          /* (N, K, 10) device: pos 3, quat xyzw 4, half extents 3, indexed by env id; NULL if K == 0 */
+  float* scratch;              /* mg_render_scratch_floats() floats, 16-byte aligned: (n_sel, P, 16) primitive records
+                                * [world rotation 9 row-major | world position 3 | size 3 | type + (colour << 8)] */
+  uint8_t* rgb;                /* (n_sel, H, W, 3) or NULL */
+  float* depth;                /* (n_sel, H, W): t along the unit ray, +inf for sky; or NULL */
+  int32_t* ids;                /* (n_sel, H, W): primitive id, -1 for sky; or NULL.  Not all three NULL */
+} mg_render_args;
+size_t mg_render_args_sizeof(void);
+/* floats of scratch for n_sel envs and num_boxes extra boxes; 0 for bad arguments or more than 512 primitives */
+size_t mg_render_scratch_floats(const mg_sim* sim, int32_t n_sel, int32_t num_boxes);
+/* MG_EINVAL (and nothing is launched or written) for: a size or fov out of range, eye == target or a view along z,
+ * all outputs NULL, n_sel < 1 (or > N with env_ids NULL), num_boxes < 0 or boxes NULL with num_boxes > 0, a NULL or
+ * misaligned scratch, a sim whose state is not bound. */
+int mg_render(mg_sim* sim, const mg_render_args* args, void* stream);
+
 /* Measurement aid (no reference counterpart; bench.py's roofline.kernel_ms): the device-side duration of the
  * fused step kernel, from the first wave's start to the last wave's end on the GPU's constant wall clock
  * (wall_clock64, hipDeviceAttributeWallClockRate), so that no launch, queue or event-packet overhead is in it.

@@ -10,6 +10,7 @@
 
 #include "dispatch.hpp"
 #include "dynamics_tensors.hpp"
+#include "render.hpp"
 #include "anymal_task.hpp"  // as reach_task.hpp: restores FMA contraction at its end
 #include "reach_task.hpp"   // before hand_task.hpp: that header leaves FMA contraction off for the rest of this file
 #include "hand_task.hpp"
@@ -1434,6 +1435,103 @@ int mg_anymal_reset_idx(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal
   hipLaunchKernelGGL(mga::k_anymal_reset_idx, dim3((n + mga::kEnvs - 1) / mga::kEnvs), dim3(64), 0,
                      (hipStream_t)stream, *ap, *views, t, st, ids, n, sim->n);
   return check_launch("mg_anymal_reset_idx");
+}
+
+// ---- Rendering: the ray caster over the collision geometry (render.hpp)
+size_t mg_render_args_sizeof(void) { return sizeof(mg_render_args); }
+
+// primitives per env: the actors' geoms, the free object and the goal, the extra boxes, the ground
+static long render_prims(const mg_sim* sim, int num_boxes) {
+  const mg_model& m = sim->host_model;
+  const int A = sim->params.agents > 1 ? sim->params.agents : 1;
+  return (long)A * m.num_geoms + (m.obj_type ? 2 : 0) + num_boxes + 1;
+}
+
+size_t mg_render_scratch_floats(const mg_sim* sim, int32_t n_sel, int32_t num_boxes) {
+  if (!sim || n_sel < 1 || num_boxes < 0) return 0;
+  const long P = render_prims(sim, num_boxes);
+  if (P > mgrd::kMaxPrims) return 0;
+  return (size_t)n_sel * (size_t)P * mgrd::kRec;
+}
+
+int mg_render(mg_sim* sim, const mg_render_args* a, void* stream) {
+  if (!sim || !a) return fail(MG_EINVAL, "mg_render: bad arguments");
+  if (!sim->bound || !sim->views.root_states || !sim->views.dof_state)
+    return fail(MG_EINVAL, "mg_render: the sim's state is not bound (mg_sim_bind)");
+  if (a->width < 1 || a->height < 1 || a->width > 16384 || a->height > 16384)
+    return fail(MG_EINVAL, "mg_render: width and height must be 1..16384");
+  if (!(a->fov_y > 0.0f) || !(a->fov_y < 3.14159265f)) return fail(MG_EINVAL, "mg_render: fov_y must be in (0, pi) radians");
+  if (!a->rgb && !a->depth && !a->ids) return fail(MG_EINVAL, "mg_render: all outputs are NULL");
+  if (a->n_sel < 1) return fail(MG_EINVAL, "mg_render: n_sel must be at least 1");
+  if (a->num_boxes < 0 || (a->num_boxes > 0 && !a->boxes))
+    return fail(MG_EINVAL, "mg_render: num_boxes must be >= 0 and boxes given when it is > 0");
+  const long P = render_prims(sim, a->num_boxes);
+  if (P > mgrd::kMaxPrims) return fail(MG_ECAPACITY, "mg_render: more than 512 primitives per env");
+  if (!a->scratch || ((uintptr_t)a->scratch & 15)) return fail(MG_EINVAL, "mg_render: scratch is NULL or not 16-byte aligned");
+  const mg_model& m = sim->host_model;
+  const int A = sim->params.agents > 1 ? sim->params.agents : 1;
+  const int n_env = sim->n / A;
+  if (m.obj_type && A != 1) return fail(MG_EINVAL, "mg_render: a model with a free object has one actor per env");
+  if (!a->env_ids && a->n_sel > n_env) return fail(MG_EINVAL, "mg_render: n_sel exceeds the env count");
+  if (m.num_geoms < 0 || m.num_geoms > MG_MAX_GEOMS || m.hull_num_planes < 0 || m.hull_num_planes > MG_MAX_HULL_PLANES)
+    return fail(MG_EINVAL, "mg_render: model tables out of range");
+  for (int g = 0; g < m.num_geoms; g++)
+    if (m.geom_node[g] < 0 || m.geom_node[g] >= m.num_nodes)
+      return fail(MG_EINVAL, "mg_render: a geom names a node outside the model");
+  {  // the camera must have a direction and a horizon
+    float f[3], n2 = 0.0f;
+    for (int k = 0; k < 3; k++) {
+      f[k] = a->target_offset[k] - a->eye_offset[k];
+      n2 += f[k] * f[k];
+    }
+    if (!(n2 > 0.0f) || !(f[0] * f[0] + f[1] * f[1] > 1e-12f * n2))
+      return fail(MG_EINVAL, "mg_render: eye and target coincide, or the view is along z");
+  }
+  const long long npix = (long long)a->width * a->height;
+  const long long tiles = (npix + mgrd::kTile - 1) / mgrd::kTile;
+  if (tiles * a->n_sel > 0x7fffffffLL || (long long)a->n_sel * A > 0x7fffffffLL - mgrd::kTeams)
+    return fail(MG_EINVAL, "mg_render: n_sel x image size exceeds the launch grid");
+  const int rows_per_env = m.obj_type ? 3 : A;
+  mgrd::SetupArgs s;
+  s.m = sim->d_model;
+  s.root = sim->views.root_states;
+  s.dof = sim->views.dof_state;
+  s.env_ids = a->env_ids;
+  s.boxes = a->boxes;
+  s.scratch = a->scratch;
+  s.n_sel = a->n_sel;
+  s.n_env = n_env;
+  s.A = A;
+  s.K = a->num_boxes;
+  s.P = (int)P;
+  s.rows_per_env = rows_per_env;
+  const long teams = (long)a->n_sel * A;
+  hipLaunchKernelGGL(mgrd::k_render_setup, dim3((unsigned)((teams + mgrd::kTeams - 1) / mgrd::kTeams)), dim3(64),
+                     sizeof(float) * 12 * mgrd::kTeams * (size_t)m.num_nodes, (hipStream_t)stream, s);
+  if (int rc = check_launch("mg_render (setup)")) return rc;
+  mgrd::TraceArgs t;
+  t.scratch = a->scratch;
+  t.m = sim->d_model;
+  t.root = sim->views.root_states;
+  t.env_ids = a->env_ids;
+  t.rgb = a->rgb;
+  t.depth = a->depth;
+  t.ids = a->ids;
+  t.W = a->width;
+  t.H = a->height;
+  t.P = (int)P;
+  t.n_env = n_env;
+  t.rows_per_env = rows_per_env;
+  t.follow = a->follow;
+  t.tiles = (int)tiles;
+  t.tan_half = tanf(0.5f * a->fov_y);
+  for (int k = 0; k < 3; k++) {
+    t.eye[k] = a->eye_offset[k];
+    t.tgt[k] = a->target_offset[k];
+  }
+  hipLaunchKernelGGL(mgrd::k_render_trace, dim3((unsigned)(tiles * a->n_sel)), dim3(mgrd::kTile),
+                     sizeof(float) * mgrd::kRec * (size_t)P + 3 * mgrd::kTile, (hipStream_t)stream, t);
+  return check_launch("mg_render (trace)");
 }
 
 }  // extern "C"

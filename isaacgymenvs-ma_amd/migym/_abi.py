@@ -179,6 +179,14 @@ class AnymalViews(C.Structure):
     _fields_ = [("commands", C.c_void_p), ("dof_targets", C.c_void_p)]
 
 
+class RenderArgs(C.Structure):
+    """mg_render_args: one ray-cast of the selected envs' collision geometry (migym/render.py)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fov_y", C.c_float), ("eye_offset", C.c_float * 3),
+                ("target_offset", C.c_float * 3), ("follow", C.c_int32), ("env_ids", C.c_void_p),
+                ("n_sel", C.c_int32), ("num_boxes", C.c_int32), ("boxes", C.c_void_p), ("scratch", C.c_void_p),
+                ("rgb", C.c_void_p), ("depth", C.c_void_p), ("ids", C.c_void_p)]
+
+
 def model_bytes(spec) -> np.ndarray:
     """mg_model POD for a ModelSpec (numpy structured scalar; pass .ctypes.data)."""
     return np.ascontiguousarray(_model.pack_model(spec))
@@ -257,6 +265,9 @@ EXPORTS = {
                                  C.POINTER(StateViews), C.c_void_p]),
     "mg_anymal_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(AnymalParams), C.POINTER(AnymalViews),
                                       C.POINTER(TaskBuffers), C.c_void_p, C.c_int32, C.c_void_p]),
+    "mg_render_args_sizeof": (C.c_size_t, []),
+    "mg_render_scratch_floats": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mg_render": (C.c_int, [C.c_void_p, C.POINTER(RenderArgs), C.c_void_p]),
 }
 
 _LIB = None
@@ -281,7 +292,7 @@ def check_layout(lib):
              "mg_dr_apply_args_sizeof": C.sizeof(DrApplyArgs), "mg_dr_noise_args_sizeof": C.sizeof(DrNoiseArgs),
              "mg_osc_args_sizeof": C.sizeof(OscArgs), "mg_reach_params_sizeof": C.sizeof(ReachParams),
              "mg_reach_views_sizeof": C.sizeof(ReachViews), "mg_anymal_params_sizeof": C.sizeof(AnymalParams),
-             "mg_anymal_views_sizeof": C.sizeof(AnymalViews)}
+             "mg_anymal_views_sizeof": C.sizeof(AnymalViews), "mg_render_args_sizeof": C.sizeof(RenderArgs)}
     for fn, py in sizes.items():
         c = getattr(lib, fn)()
         if c != py:

@@ -29,6 +29,32 @@ TASK_INFO["FrankaReachMA"] = (None, None, 0, 6, 1.0 + 0.05 / 2 + 0.1, 8)
 # model on the (32, 32, 48, 48, 192) instance (37 geoms need MG >= 48 anyway)
 TASK_INFO["Anymal"] = (None, None, 48, 12, 0.62, 48)
 
+# VecTask.render / render_envs: the default frame and camera of each task (migym/render.py).  eye / target are offsets
+# from the root position of the env's actor 0 (follow) or from the env origin; cfg["env"]["render"] overrides any key.
+RENDER_DEFAULTS = {
+    "Cartpole": dict(width=320, height=240, fov_deg=60.0, eye=(4.0, 0.0, 0.5), target=(0.0, 0.0, 0.0), follow=True),
+    "Ant": dict(width=320, height=240, fov_deg=60.0, eye=(2.5, -2.5, 1.5), target=(0.0, 0.0, 0.0), follow=True),
+    "Humanoid": dict(width=320, height=240, fov_deg=60.0, eye=(2.2, -2.2, 0.8), target=(0.0, 0.0, -0.2), follow=True),
+    "ShadowHand": dict(width=320, height=240, fov_deg=60.0, eye=(0.45, -0.85, 0.45), target=(0.0, -0.3, 0.1),
+                       follow=True),
+    "MAAnt": dict(width=320, height=240, fov_deg=60.0, eye=(4.0, -4.0, 3.0), target=(0.0, 0.0, 0.0), follow=False),
+    "FrankaReachMA": dict(width=320, height=240, fov_deg=60.0, eye=(1.2, -1.2, 1.9), target=(0.0, 0.0, 1.15),
+                          follow=False),
+    "Anymal": dict(width=320, height=240, fov_deg=60.0, eye=(1.6, -1.6, 0.9), target=(0.0, 0.0, -0.1), follow=True),
+}
+
+
+def render_settings(task: str, cfg: dict) -> dict:
+    """RENDER_DEFAULTS[task] with the overrides of cfg["env"]["render"] (width, height, fov_deg, eye, target, follow)"""
+    d = dict(RENDER_DEFAULTS.get(task, RENDER_DEFAULTS["Ant"]))
+    over = dict((cfg.get("env", {}) or {}).get("render", {}) or {})
+    unknown = set(over) - set(d)
+    if unknown:
+        raise ValueError(f"env.render: unknown keys {sorted(unknown)} (known: {sorted(d)})")
+    d.update(over)
+    return d
+
+
 # build-defined solver constants (DESIGN.md §Physics)
 BAUMGARTE = 0.2
 LIMIT_MARGIN = 0.1

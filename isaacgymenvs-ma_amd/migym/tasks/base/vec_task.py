@@ -505,7 +505,37 @@ class VecTask(DomainRandomizationMixin, Env):
         (parity tests replay the reference's torch draws through this)."""
         self._noise = None if noise is None else noise.to(self.device, torch.float32).contiguous()
 
+    # ---------------------------------------------------------------------------------- rendering
+    _renderer = None
+
+    def renderer(self):
+        """the task's Renderer (migym/render.py), created on first use from taskdefs.render_settings"""
+        r = self._renderer
+        if r is None:
+            from migym.render import Renderer
+            st = taskdefs.render_settings(self.task_name, self.cfg)
+            r = self._renderer = Renderer(self._lib, self.sim, self.model_spec, self.num_envs, self.num_agents,
+                                          self.device, st["width"], st["height"], fov_deg=st["fov_deg"],
+                                          eye_offset=st["eye"], target_offset=st["target"], follow=st["follow"])
+        return r
+
+    def render_boxes(self):
+        """task-owned boxes the renderer draws after the model's geoms: (N, K, 10) fp32 [pos 3 | quat xyzw 4 | half
+        extents 3] or None (FrankaReachMA: its target cubes)"""
+        return None
+
+    def render_envs(self, env_ids=None, **kw):
+        """Images of the listed envs (None = all) as device tensors, asynchronously on the current stream: the
+        pixel-observation path.  Keywords as Renderer.render (rgb / depth / ids / stream); the returned tensors are
+        overwritten by the next call.  Reads the state only: no step output depends on it."""
+        kw.setdefault("boxes", self.render_boxes())
+        return self.renderer().render(env_ids, **kw)
+
     def render(self, mode="rgb_array"):
+        """vec_task.py render: with virtual_screen_capture, env 0's frame as an (H, W, 3) uint8 array (the collision
+        geometry, ray-cast on the device; one host copy); otherwise None (there is no viewer window)."""
+        if self.virtual_screen_capture and mode == "rgb_array":
+            return self.render_envs([0], rgb=True)["rgb"][0].cpu().numpy()
         return None
 
     def close(self):

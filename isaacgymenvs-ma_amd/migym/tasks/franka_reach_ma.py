@@ -167,6 +167,12 @@ class FrankaReachMA(VecTask):
         rv.dof_targets, rv.dof_actuation = _abi.ptr(self.dof_targets), _abi.ptr(self.dof_actuation)
         self._reach_views = rv
 
+    def render_boxes(self):
+        """the target cubes, as the renderer's extra boxes"""
+        h = 0.5 * float(self.cubeA_size)
+        half = torch.full((self.num_envs, self.num_targets, 3), h, device=self.device, dtype=torch.float32)
+        return torch.cat([self._cubeA_state[..., 0:7], half], dim=-1).contiguous()
+
     def allocate_buffers(self):
         dev, n = self.device, self.num_actors
         self.obs_buf = torch.zeros((n, self.num_obs), device=dev, dtype=torch.float)
