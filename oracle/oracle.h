@@ -57,6 +57,10 @@ int orc_contacts(const mg_model* m, const mg_sim_params* p, const float* root13,
  * geom-object pair without a contact */
 int orc_contacts_marks(const mg_model* m, const mg_sim_params* p, const float* root13, const float* dof2, double delta,
                        double* out, int32_t cap, int32_t* pair_lost);
+/* per row of orc_contacts_marks (same arguments): the part of collide() that emitted it (1 geom on the ground, 2 the
+ * object on the ground, 3 self pair, 4 / 5 / 6 hull vertices / faces / exact candidates, 7 another geom-object) */
+int orc_contacts_phases(const mg_model* m, const mg_sim_params* p, const float* root13, const float* dof2, double delta,
+                        int32_t* phases, int32_t cap);
 /* egg narrowphase KAT hook (GJK + shrunk-core retry): kind 0 segment p0,p1 / kind 1 box c, R (row-major),
  * h, plus radius, vs the origin-centred ellipsoid e; out = point(3), normal(3), distance */
 int orc_ellipsoid_contact(int32_t kind, const double* shape, double radius, const double* e, double* out);

@@ -67,8 +67,13 @@ static __thread int orc_tie_hit = 0;
  * the geometry does not pin -- an end point or a box edge / corner at the closest point) */
 static __thread int orc_amb_hit = 0;  /* bit 16 for the whole step (an ambiguous decision that made no contact) */
 static __thread int orc_amb_pend = 0; /* an ambiguous decision in the current geom-object candidate set */
+static __thread int orc_amb_lost_at = -1; /* list position of the first pair lost to an ambiguity (bit 128) */
 static __thread int orc_ill_next = 0;
 static __thread int orc_edge_next = 0; /* the contact being pushed is box_box_edge's */
+/* where collide() is: the kernel emits each of these in a pass of its own, with its own capacity guard */
+enum { ORC_PH_GROUND = 1, ORC_PH_OBJ_GROUND, ORC_PH_PAIR, ORC_PH_HULL_VERT, ORC_PH_HULL_FACE, ORC_PH_HULL_EXACT,
+       ORC_PH_GEOM_OBJ };
+static __thread int orc_phase = 0;
 static __thread int orc_pb_ill = 0;   /* the last point_box: outside, two or more axes clamped, nearer than NORMAL_ILL */
 static __thread int orc_cvx_ill = 0;  /* the last cvx_contact: an MPR depth below NORMAL_ILL */
 static __thread int orc_hull_ill = 0; /* the last hull_core_contacts: a GJK distance below NORMAL_ILL */
@@ -202,6 +207,7 @@ typedef struct {
   int ill;   /* ill-conditioned normal (orc_step_flips bit 32) */
   int amb;   /* made by a geom-object candidate set with a decision in its ambiguity band (bit 16) */
   int edge;  /* box_box_edge's contact (orc_contacts_marks bit 16: what a state set reaches) */
+  int phase; /* the part of collide() that emitted it (ORC_PH_*; orc_contacts_phases) */
 } contact;
 
 static int nv_of(const mg_model* m) { return (m->fixed_base ? 0 : 6) + m->num_dofs; }
@@ -488,6 +494,7 @@ static int push_contact(contact* out, int n, int cap, int nodeA, int gA, int nod
   c->ill = orc_ill_next;
   c->amb = 0;
   c->edge = orc_edge_next;
+  c->phase = orc_phase;
   orc_ill_next = 0;
   orc_edge_next = 0;
   return n + 1;
@@ -834,6 +841,7 @@ static int geom_object(const mg_model* m, const kin* k, int g, real off, contact
     const real hg[3] = {m->geom_size[g][0], m->geom_size[g][1], m->geom_size[g][2]};
     if (!hull_box_near(c, R, hg, k->op, sqrt(dot3(hb, hb)), off)) return n;
     /* the hull's vertices against the object */
+    orc_phase = ORC_PH_HULL_VERT;
     for (int v = 0; v < m->hull_num_verts; v++) {
       real l[3] = {m->hull_vert[v][0], m->hull_vert[v][1], m->hull_vert[v][2]}, w[3], pl[3];
       matvec3(R, l, w);
@@ -850,6 +858,7 @@ static int geom_object(const mg_model* m, const kin* k, int g, real off, contact
       }
     }
     /* the object's vertices against the hull's faces (normal: minus the face normal) */
+    orc_phase = ORC_PH_HULL_FACE;
     for (int v = 0; v < 8; v++) {
       real l[3] = {(v & 1 ? 1 : -1) * hb[0], (v & 2 ? 1 : -1) * hb[1], (v & 4 ? 1 : -1) * hb[2]}, w[3], dl[3], pl[3];
       from_obj_pt(k, l, w);
@@ -869,6 +878,7 @@ static int geom_object(const mg_model* m, const kin* k, int g, real off, contact
       }
     }
     /* edge against edge / edge across a face: the exact distance of the hull and the box */
+    orc_phase = ORC_PH_HULL_EXACT;
     return hull_object_exact(m, k, g, c, R, off, out, n, cap);
   }
   if (ty != MG_GT_BOX) return n;
@@ -2071,6 +2081,7 @@ static int geom_object_convex(const mg_model* m, const kin* k, int g, real off, 
     const real orad = ot == MG_GT_ELLIPSOID ? fmax(os[0], fmax(os[1], os[2])) : os[0] + os[1];
     if (!hull_box_near(c, R, hg, k->op, orad, off)) return n;
     if (ot == MG_GT_ELLIPSOID) {
+      orc_phase = ORC_PH_HULL_FACE;
       /* egg: the hull's face planes against the ellipsoid's support points (the plane distance of the egg's
        * point farthest along -n_f, largest over the faces): exact where a hull face is the nearest feature,
        * a lower bound near hull edges; normal minus that face's normal, point halfway across the gap */
@@ -2109,6 +2120,7 @@ static int geom_object_convex(const mg_model* m, const kin* k, int g, real off, 
     const real ro = os[0];
     real p0[3], p1[3];
     for (int a = 0; a < 3; a++) { p0[a] = k->op[a] - k->oR[a][2] * os[1]; p1[a] = k->op[a] + k->oR[a][2] * os[1]; }
+    orc_phase = ORC_PH_HULL_VERT;
     for (int v = 0; v < m->hull_num_verts; v++) {
       real l[3] = {m->hull_vert[v][0], m->hull_vert[v][1], m->hull_vert[v][2]}, w[3], s, t, q[3], dv[3];
       matvec3(R, l, w);
@@ -2125,6 +2137,7 @@ static int geom_object_convex(const mg_model* m, const kin* k, int g, real off, 
         n = push_contact(out, n, cap, nd, g, OBJ_NODE, -2, pw, nw, d);
       }
     }
+    orc_phase = ORC_PH_HULL_FACE;
     for (int e = 0; e < 2; e++) {
       const real* pe = e == 0 ? p0 : p1;
       real dl[3], pl[3];
@@ -2144,6 +2157,7 @@ static int geom_object_convex(const mg_model* m, const kin* k, int g, real off, 
       }
     }
     /* the pen's segment interior across the hull (a ridge, or a face its ends overhang): exact distance */
+    orc_phase = ORC_PH_HULL_EXACT;
     return hull_object_exact(m, k, g, c, R, off, out, n, cap);
   }
   if (ot == MG_GT_ELLIPSOID) {
@@ -2239,6 +2253,7 @@ static int geom_object_convex(const mg_model* m, const kin* k, int g, real off, 
 static int collide(const mg_model* m, const mg_sim_params* p, const kin* k, contact* out, int cap) {
   int n = 0;
   real off = p->contact_offset;
+  orc_phase = ORC_PH_GROUND;
   for (int g = 0; g < m->num_geoms; g++) {
     if (!(m->geom_filter[g] & MG_COLLIDE_GROUND)) continue;
     int nd = m->geom_node[g], ty = m->geom_type[g];
@@ -2270,6 +2285,7 @@ static int collide(const mg_model* m, const mg_sim_params* p, const kin* k, cont
       }
     }
   }
+  orc_phase = ORC_PH_OBJ_GROUND;
   if (m->obj_type == MG_GT_BOX) {
     for (int corner = 0; corner < 8; corner++) {
       real l[3] = {(corner & 1 ? 1 : -1) * m->obj_size[0], (corner & 2 ? 1 : -1) * m->obj_size[1],
@@ -2292,6 +2308,7 @@ static int collide(const mg_model* m, const mg_sim_params* p, const kin* k, cont
   }
   /* explicit MJCF pairs: in contact from zero distance (margin 0); orc_step_flips moves that threshold too */
   const real poff = m->pair_mjcf ? orc_pair_offset : off;
+  orc_phase = ORC_PH_PAIR;
   for (int pi = 0; pi < m->num_pairs; pi++) {
     int ga = m->pair[pi][0], gb = m->pair[pi][1];
     real a0[3], a1[3], b0[3], b1[3], ra, rb;
@@ -2349,11 +2366,15 @@ static int collide(const mg_model* m, const mg_sim_params* p, const kin* k, cont
            * uses one of them); one that left the pair without any contact marks the step */
           const int n0 = n;
           orc_amb_pend = 0;
+          orc_phase = ORC_PH_GEOM_OBJ;
           n = m->obj_type == MG_GT_BOX ? geom_object(m, k, g, off, out, n, cap)
                                        : geom_object_convex(m, k, g, off, out, n, cap);
           if (orc_amb_pend) {
             for (int i = n0; i < n; i++) out[i].amb = 1;
-            if (n == n0) orc_amb_hit = 1;
+            if (n == n0) {
+              orc_amb_hit = 1;
+              if (orc_amb_lost_at < 0) orc_amb_lost_at = n0;
+            }
           }
           orc_amb_pend = 0;
         }
@@ -2985,9 +3006,10 @@ int orc_contacts_full(const mg_model* m, const mg_sim_params* p, const float* ro
  *   4  gap within delta of its threshold, below it (the contact is in orc_contacts_full's list)
  *   8  gap at or above its threshold (only the widened list holds it)
  *  16  box_box_edge's contact (not an exemption: what the state sets must reach)
- * *pair_lost = 1 when an ambiguous decision left a geom-object pair without any contact.  Returns the count. */
-int orc_contacts_marks(const mg_model* m, const mg_sim_params* p, const float* root13, const float* dof2, double delta,
-                       double* out, int32_t cap, int32_t* pair_lost) {
+ * *pair_lost = 1 when an ambiguous decision left a geom-object pair without any contact.  Returns the count.
+ * phases (orc_contacts_phases; out may then be NULL): per row the part of collide() that emitted it (ORC_PH_*). */
+static int contacts_marks(const mg_model* m, const mg_sim_params* p, const float* root13, const float* dof2, double delta,
+                          double* out, int32_t cap, int32_t* pair_lost, int32_t* phases) {
   astate s;
   kin k;
   memset(&s, 0, sizeof(s));
@@ -3006,6 +3028,8 @@ int orc_contacts_marks(const mg_model* m, const mg_sim_params* p, const float* r
   if (pair_lost) *pair_lost = orc_amb_hit;
   orc_amb_hit = 0;
   for (int i = 0; i < nc; i++) {
+    if (phases) phases[i] = con[i].phase;
+    if (!out) continue;
     real* o = out + 12 * i;
     o[0] = con[i].nodeA; o[1] = con[i].geomA; o[2] = con[i].nodeB; o[3] = con[i].geomB;
     for (int a = 0; a < 3; a++) { o[4 + a] = con[i].p[a]; o[7 + a] = con[i].n[a]; }
@@ -3017,6 +3041,20 @@ int orc_contacts_marks(const mg_model* m, const mg_sim_params* p, const float* r
     o[11] = mk;
   }
   return nc;
+}
+
+int orc_contacts_marks(const mg_model* m, const mg_sim_params* p, const float* root13, const float* dof2, double delta,
+                       double* out, int32_t cap, int32_t* pair_lost) {
+  return contacts_marks(m, p, root13, dof2, delta, out, cap, pair_lost, NULL);
+}
+
+/* per row of orc_contacts_marks (same arguments, same rows): the part of collide() that emitted it -- 1 an
+ * articulation geom on the ground, 2 the object on the ground, 3 a self pair, 4 / 5 / 6 the convex-mesh geom's
+ * vertices / faces / exact candidates against the object, 7 another geom against the object (ORC_PH_*) -- for tests
+ * that place the capacity cut inside each.  Returns the count. */
+int orc_contacts_phases(const mg_model* m, const mg_sim_params* p, const float* root13, const float* dof2, double delta,
+                        int32_t* phases, int32_t cap) {
+  return contacts_marks(m, p, root13, dof2, delta, NULL, cap, NULL, phases);
 }
 
 /* The discontinuities of the build's physics that env `e`'s gym.simulate (state views as orc_simulate_views)
@@ -3035,7 +3073,13 @@ int orc_contacts_marks(const mg_model* m, const mg_sim_params* p, const float* r
  *  32  a contact in use whose normal is ill-conditioned: the direction of a core distance below NORMAL_ILL
  *      (0.5 mm) that the geometry does not pin (an end point, a box edge or corner at the closest point; an
  *      MPR or hull-GJK depth), so that a 1e-7 m difference of the state turns it by ~1e-4 rad
- *  64  the angular-velocity cap clipped a hinge rate to an ill-conditioned interval end (clamp_ang_vel) */
+ *  64  the angular-velocity cap clipped a hinge rate to an ill-conditioned interval end (clamp_ang_vel)
+ * 128  past capacity, the cut near a threshold: the untruncated list (thresholds out by delta, a pair lost to an
+ *      ambiguity counted) holds more than min(max_contacts, MAXC) entries, and an entry within delta of its
+ *      threshold on either side, an ambiguous one or a lost pair stands before the position where the entries every
+ *      implementation emits reach the capacity.  Unlike bit 1 it does not ask whether the row is used: the entry
+ *      shifts which later contact is dropped.  Unreachable while the list fits.  A state with MAXC or more
+ *      candidates cannot be counted and is not a valid input of a past-capacity test. */
 int orc_step_flips(const mg_model* m0, const mg_sim_params* p, const mg_state_views* v, int32_t e, double delta,
                    double df) {
   const mg_model* m = m0;
@@ -3077,6 +3121,29 @@ int orc_step_flips(const mg_model* m0, const mg_sim_params* p, const mg_state_vi
       const real fe = m->drive_kp[i] * ((tgt ? tgt[i - 1] : 0.0) - s.qj[i]) - m->damping[i] * s.qd[i];
       const real lim = m->effort_limit[i];
       if (fabs(fabs(fe) - lim) < df * (lim > 1e-6 ? lim : 1e-6)) flags |= 4;
+    }
+    /* bit 128: the cut near a threshold.  The list without truncation (MAXC), thresholds moved out by delta: when
+     * it holds more than cap entries, an entry that one implementation emits and another may not (within delta of
+     * its threshold on either side, ambiguous, or a pair lost to an ambiguity) moves every later entry by a slot,
+     * and so decides which contact the cut drops -- whether or not its own row is used.  `firm` counts the entries
+     * every implementation emits; once it reaches cap, what follows lies behind the cut for all of them. */
+    {
+      static __thread kin kc;
+      contact all[MAXC];
+      const int cap = p->max_contacts < MAXC ? p->max_contacts : MAXC;
+      forward_kinematics(m, &s, &kc);
+      orc_pair_offset = delta;
+      orc_tie_delta = delta;
+      orc_amb_lost_at = -1;
+      const int na = collide(m, &pw, &kc, all, MAXC);
+      const int lost = orc_amb_lost_at;
+      orc_amb_lost_at = -1;
+      if (na + (lost >= 0) > cap)
+        for (int i = 0, firm = 0; i < na && firm < cap; i++) {
+          const real thr = (m->pair_mjcf && all[i].nodeB >= 0) ? 0.0 : p->contact_offset;
+          if (i == lost || all[i].amb || !(all[i].d < thr - delta)) flags |= 128;
+          if (!all[i].amb && all[i].d < thr - delta) firm++;
+        }
     }
     /* the solve with the thresholds moved out (its collide also reports seg_box_sat ties) */
     astate sw = s;

@@ -153,6 +153,19 @@ def contacts_marks(model_np, sp, root13, dof2, delta=1e-4, cap=64):
     return r[:, :11].copy(), r[:, 11].astype(np.int32), bool(lost[0])
 
 
+PH_GROUND, PH_OBJ_GROUND, PH_PAIR, PH_HULL_VERT, PH_HULL_FACE, PH_HULL_EXACT, PH_GEOM_OBJ = range(1, 8)
+
+
+def contacts_phases(model_np, sp, root13, dof2, delta=1e-4, cap=64):
+    """per row of contacts_marks (same arguments, same rows): the part of collide() that emitted it (PH_*)"""
+    out = np.zeros(cap, np.int32)
+    lib().orc_contacts_phases.argtypes = [C.c_void_p, C.POINTER(_abi.SimParams), C.c_void_p, C.c_void_p, C.c_double,
+                                          C.c_void_p, C.c_int32]
+    n = lib().orc_contacts_phases(model_np.ctypes.data, C.byref(sp), p(f32(root13)), p(f32(dof2)), float(delta), p(out),
+                                  cap)
+    return out[:n].copy()
+
+
 def box_box_edge(c, R, h, hb, off):
     """edge-edge contact of hand box (c, R, h) against the object box hb (object frame): None or
     (point, normal from the object to the hand box, separation)"""
@@ -192,7 +205,9 @@ def ellipsoid_contact(kind, shape, radius, e):
 def step_flips(model_np, sp, host, delta=1e-4, df=1e-2):
     """per env of a HostEnv / HandHostEnv holding a step's physics input (after pre-physics): the bit mask of
     orc_step_flips (1 contact threshold in use, 2 limit threshold in use, 4 drive near saturation, 8 seg_box_sat
-    tie) over the substeps of one gym.simulate"""
+    tie, 16 ambiguous narrowphase decision, 32 ill-conditioned normal, 64 ill-conditioned angular-velocity cap,
+    128 past max_contacts with a candidate near its threshold before the cut) over the substeps of one gym.simulate.
+    Past capacity the input must have fewer than 64 candidates: the oracle's own list ends there"""
     v = host.views()
     return np.array([lib().orc_step_flips(model_np.ctypes.data, C.byref(sp), C.byref(v), e, delta, df)
                      for e in range(host.n)], np.int32)

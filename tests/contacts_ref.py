@@ -209,6 +209,16 @@ def hand_set(name, n=256):
     where, kind = name.split("-") if "-" in name else (name, "block")
     if where == "hull":
         spec, sp, tp, h = H.hull_exact_states(kind, n, np.random.default_rng(13))
+    elif where == "ground":
+        # the object lying on the ground plane below the hand, tilted by ~0.01 rad, its centre within 1 mm of resting
+        # height: several of its lower corners within the contact offset (only the list-cut tests use this set)
+        spec, sp, tp = H.setup(kind=kind)
+        rng = np.random.default_rng(19)
+        h = H.hand_states(spec, tp, n, rng, H.PALM_DZ[kind])
+        yaw, tilt = rng.uniform(-np.pi, np.pi, n), rng.normal(0, 0.005, (n, 2))
+        q = np.stack([tilt[:, 0], tilt[:, 1], np.sin(yaw / 2), np.cos(yaw / 2)], -1)
+        h.root[:, 1, 3:7] = q / np.linalg.norm(q, axis=-1, keepdims=True)
+        h.root[:, 1, 2] = float(M.pack_model(spec)["obj_size"][2]) + rng.uniform(-1e-3, 1e-3, n)
     else:
         spec, sp, tp = H.setup(kind=kind)
         rng = np.random.default_rng({"palm": 5, "forearm": 11, "fingers": 17}[where])
@@ -264,6 +274,84 @@ def tree_set(case, kind):
     spec, sp = TP.spec_of(case), TP.sim_params(case)
     root, dof, act, _ = TP.states(case, kind)
     return spec, sp, M.pack_model(spec), root, dof, act
+
+
+# ------------------------------------------------------------------------------------------------ a cut in every phase
+# (phase, state set, max_contacts k): the capacity cut between the oracle's entries k - 1 and k falls inside that part
+# of collide() -- both entries emitted by it, the ground phases' by the same geom -- in at least CUT_ENVS envs of the
+# set, so that each pass's own `slot < cap` guard decides a contact.  Sets: hand:<hand_set>, tree:<case>:<kind>,
+# task:<task>:<envs>.  k = 24 / 48 on the overflow trees is the instance's MC (slot k is the first one past the
+# per-team arrays).  "compact": any cut, the task model on the compact layout.  hand:ground-block is a set of its
+# own (hand_set): the cube lying on the ground plane, which no other set reaches.
+CUT_ENVS = 8
+CUTS = (
+    ("capsule ends, one pass", "tree:T16-fixed-round:overflow", 2),
+    ("capsule ends, one pass", "tree:T16-fixed-round:overflow", 24),
+    ("box corners", "tree:T16-fixed:overflow", 21),
+    ("object on the ground", "hand:ground-block", 2),
+    ("self pairs", "tree:T32-free:overflow", 48),
+    ("self pairs", "hand:fingers", 1),
+    ("hull vertices", "hand:forearm-block", 1),
+    ("hull faces", "hand:forearm-block", 2),
+    ("exact hull", "hand:hull-pen", 1),
+    ("exact hull", "hand:forearm-pen", 4),
+    ("egg staged", "hand:palm-egg", 2),
+    ("geom-object map", "hand:palm-block", 2),
+    ("geom-object map", "hand:palm-pen", 3),
+    ("compact", "task:Ant:256", 2),
+    ("compact", "task:Humanoid:128", 4),
+)
+_PHASES = {"object on the ground": O.PH_OBJ_GROUND, "capsule ends, one pass": O.PH_GROUND, "box corners": O.PH_GROUND,
+           "self pairs": O.PH_PAIR,
+           "hull vertices": O.PH_HULL_VERT, "hull faces": O.PH_HULL_FACE, "exact hull": O.PH_HULL_EXACT,
+           "egg staged": O.PH_GEOM_OBJ, "geom-object map": O.PH_GEOM_OBJ}
+
+
+def cut_id(cut):
+    return f"{cut[0]}-{cut[1]}-{cut[2]}".replace(" ", "_").replace(",", "")
+
+
+def cut_set(where):
+    """(spec, sp, mnp, root, dof, extra, kind, lists key) of a CUTS set; extra: the hand's host env, or the actuation"""
+    what, name, *rest = where.split(":")
+    if what == "hand":
+        spec, sp, mnp, root, dof, h = hand_set(name)
+        return spec, sp, mnp, root, dof, h, kind_of(name), ("hand", name)
+    if what == "tree":
+        import tree_physics_ref as TP
+        spec, sp, mnp, root, dof, act = tree_set(TP.CASES[name], rest[0])
+        return spec, sp, mnp, root, dof, act, "none", ("tree", name, rest[0])
+    spec, sp, tp, mnp, root, dof, act = task_set(name, int(rest[0]))
+    return spec, sp, mnp, root, dof, act, "none", ("task", name, int(rest[0]))
+
+
+def cut_envs(cut):
+    """the envs of the set in which the cut at k falls inside the phase, decided from the fp64 oracle's list at the
+    thresholds themselves (by the emitting part and the geom of entries k - 1 and k)"""
+    phase, where, k = cut
+    spec, sp, mnp, root, dof, _, _, key = cut_set(where)
+    lists = cached_lists(key, mnp, sp, root, dof)
+    ground_round = not any(g.gtype in (M.GT_BOX, M.GT_CONVEX) for g in spec.geoms)
+    hits = []
+    for e, (rows, marks, _) in enumerate(lists):
+        real = (marks & BAND_OUT) == 0
+        if real.sum() <= k:
+            continue
+        if phase == "compact":
+            hits.append(e)
+            continue
+        ph = O.contacts_phases(mnp, sp, np.asarray(root[e]).ravel(), dof[e], DELTA, 64)[real]
+        a, b = rows[real][k - 1], rows[real][k]
+        ok = ph[k - 1] == ph[k] == _PHASES[phase]
+        if ok and ph[k] == O.PH_GROUND:
+            gt = spec.geoms[int(b[1])].gtype
+            want = gt == M.GT_CAPSULE and ground_round if phase.startswith("capsule") else gt == M.GT_BOX
+            ok = a[1] == b[1] and want
+        if ok and ph[k] == O.PH_GEOM_OBJ:
+            ok = (int(mnp["obj_type"]) == M.GT_ELLIPSOID) == (phase == "egg staged")
+        if ok:
+            hits.append(e)
+    return hits
 
 
 TASK_ROLLOUT = {"Ant": 40, "Humanoid": 25}   # control steps from the reset pose to feet on the ground

@@ -13,6 +13,8 @@ its substeps, at a discontinuity:
   * a joint-limit row within STEP_DELTA of the limit margin, used by the solve (the same rule);
   * a PD drive whose explicit force is within STEP_DF (relative) of its effort limit (implicit <-> saturated);
   * a capsule core inside a box whose two least push-out faces tie (seg_box_sat);
+  * past max_contacts, a contact candidate within STEP_DELTA of its threshold on either side (or an ambiguous one)
+    that precedes the cut: used or not, it shifts which later contact the cut drops (bit 128);
 
 or where the oracle is itself sensitive (one step of the env alone with positions moved by 1e-6 moves its
 observation by >= 1/4 of the GPU-vs-oracle gap).  The fraction of ALL env-steps these predicates exempt is
@@ -236,7 +238,9 @@ def step_flags(mnp, sp, host, delta=STEP_DELTA, df=STEP_DF):
     pre_physics, optionally with env_props): bit 1 contact threshold in use, 2 limit threshold in use, 4 drive
     near saturation, 8 seg_box_sat tie, 16 a narrowphase decision within its ambiguity band, 32 an
     ill-conditioned contact normal (core distance / MPR depth below 0.5 mm), 64 the angular-velocity cap clipped a
-    hinge rate to an ill-conditioned interval end"""
+    hinge rate to an ill-conditioned interval end, 128 more candidates than max_contacts with one near its
+    threshold (or ambiguous) at or before the cut (never set while the candidates fit; the input must have fewer
+    than 64 of them)"""
     return O.step_flips(mnp, sp, host, delta, df)
 
 
@@ -273,7 +277,7 @@ def assert_steps_explained(test, bad, flags, sens=None, reach_cap=REACH_CAP, sen
     total = bad.size
     rec = {"env_steps": int(total), "disagreeing": int(bad.sum()), "flagged_reach": float(flagged.mean()),
            "explained_by_flags": int((bad & flagged).sum()), "explained_by_sensitivity": nsens,
-           "bits": {str(b): float(((np.asarray(flags) & b) != 0).mean()) for b in (1, 2, 4, 8, 16, 32, 64)}}
+           "bits": {str(b): float(((np.asarray(flags) & b) != 0).mean()) for b in (1, 2, 4, 8, 16, 32, 64, 128)}}
     unexplained = np.argwhere(bad & ~why)
     rec["unexplained"] = int(len(unexplained))
     rec["allowed_unexplained"] = float(allow_unexplained)

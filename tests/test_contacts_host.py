@@ -79,6 +79,27 @@ def test_truncated_list_is_a_prefix():
         CR.compare("truncated", [p[:3] for p in plain], lists, "block", max_contacts=4, record=False)
 
 
+@pytest.mark.parametrize("cut", CR.CUTS, ids=CR.cut_id)
+def test_twin_list_cut_in_every_phase(cut):
+    """max_contacts = k with the cut inside one part of collide() (contacts_ref.CUTS) in at least CUT_ENVS envs,
+    decided from the oracle's list; the twin's list at that capacity is the oracle's prefix, through the unchanged rule.
+    And the rule sees a cut one slot late (k + 1 rows where more are due) or early"""
+    phase, where, k = cut
+    spec, sp, mnp, root, dof, _, kind, key = CR.cut_set(where)
+    hits = CR.cut_envs(cut)
+    assert len(hits) >= CR.CUT_ENVS, f"{cut}: the cut falls inside the phase in {len(hits)} envs"
+    lists = CR.cached_lists(key, mnp, sp, root, dof)
+    mark_cap = CR.MARK_CAP_HULL if where.startswith("hand:hull") else CR.MARK_CAP
+    test = f"test_twin_list_cut_in_every_phase[{CR.cut_id(cut)}]"
+    st = CR.compare(test, CR.twin_lists(mnp, sp, root, dof, cap=k), lists, kind, max_contacts=k, mark_cap=mark_cap)
+    CR.PS._REPORT[test]["cut"] = {"envs_in_phase": len(hits), "k": k}
+    assert st["unexplained"] == 0 and st["matched"] > 0
+    for late in (k + 1, k - 1):
+        with pytest.raises(AssertionError):
+            CR.compare(test, CR.twin_lists(mnp, sp, root, dof, cap=late), lists, kind, max_contacts=k,
+                       mark_cap=mark_cap, record=False)
+
+
 def _turn(n, angle):
     a = np.cross(n, [1.0, 0.0, 0.0] if abs(n[0]) < 0.9 else [0.0, 1.0, 0.0])
     a /= np.linalg.norm(a)

@@ -6,7 +6,8 @@ writes the list out; tests/contacts_ref.py compares it with the oracle's: the sa
 and normals within 4 x the error of the oracle's fp32 twin (tests/test_contacts_host.py), exemptions only inside the
 oracle's threshold band and ambiguity marks and capped.  State sets: the hand tests' (palm, forearm, exact hull,
 curled fingers), every tree_physics_ref case dropped and settled, Ant and Humanoid on their feet in both layouts, two
-truncated lists; and the read-out leaves no trace in the state or in a later simulate.
+truncated lists, and lists cut by max_contacts inside every part of collide() (contacts_ref.CUTS); and the read-out
+leaves no trace in the state or in a later simulate.
 """
 import copy
 import ctypes as C
@@ -186,6 +187,26 @@ def test_truncated_tree_list_is_the_oracles_prefix(lib):
     got, lanes, _, _ = read_contacts(lib, mnp, sp4, len(root), lambda: _loco_views(spec, root, dof, act))
     assert lanes == case.lanes and max(len(g) for g in got) == 4
     CR.compare("test_truncated_tree_list_is_the_oracles_prefix", got, lists, "none", max_contacts=4)
+
+
+@pytest.mark.parametrize("cut", CR.CUTS, ids=CR.cut_id)
+def test_list_cut_in_every_phase_is_the_oracles_prefix(lib, cut, monkeypatch):
+    """max_contacts = k with the cut inside one part of collide() (contacts_ref.CUTS): each pass's own capacity guard
+    drops a contact in at least CUT_ENVS envs (asserted from the oracle's list), the overflow trees' at the last slot
+    of the per-team arrays (k = MC), Ant and Humanoid on the compact layout"""
+    phase, where, k = cut
+    if phase == "compact":
+        monkeypatch.setenv("MIGYM_LAYOUT", "compact")
+    spec, sp, mnp, root, dof, extra, kind, key = CR.cut_set(where)
+    assert len(CR.cut_envs(cut)) >= CR.CUT_ENVS
+    lists = CR.cached_lists(key, mnp, sp, root, dof)
+    views = (lambda: _hand_views(extra)) if where.startswith("hand") else (lambda: _loco_views(spec, root, dof, extra))
+    got, lanes, compact, _ = read_contacts(lib, mnp, CR.with_max_contacts(sp, k), len(root), views)
+    assert compact == (phase == "compact") and max(len(g) for g in got) == k
+    if where.startswith("tree") and where.endswith("overflow"):
+        assert k <= sp.max_contacts and all(len(g) == k for g in got)   # every overflow state fills the list
+    CR.compare(f"test_list_cut_in_every_phase_is_the_oracles_prefix[{CR.cut_id(cut)}]", got, lists, kind,
+               max_contacts=k, mark_cap=CR.MARK_CAP_HULL if where.startswith("hand:hull") else CR.MARK_CAP)
 
 
 # ------------------------------------------------------------------------------------------------ non-interference

@@ -23,7 +23,8 @@ shfl_xor(., 32) halves of the team reductions, the full-wave masks); the second 
 below slides, slides in a free-base tree; a free base with more than 21 DOFs; a fixed base with several DOF chains;
 limit and contact rows beyond the team's lanes.  Each case runs 1, 6 and 66 actors (a lone team; a partial wave at 4
 and at 2 actors per wave; several blocks with a ragged tail), from dropped and from settled states, and once per
-instance with the TGS solver.
+instance with the TGS solver.  Past contact capacity: the overflow states (max_contacts = MC, every candidate
+list longer) on six of the cases, once with TGS, and the dropped states of two cases at max_contacts = 8.
 
 One mg_sim_simulate from the states of the oracle's step; every env within the project's one-step tolerances
 (positions 2e-4, velocities 2e-3 + 2e-3 |v|, DOF forces, sensors and net contact forces 1 % of the batch's largest)
@@ -56,12 +57,12 @@ def T(a):
     return torch.as_tensor(np.ascontiguousarray(a)).to(DEV, torch.float32).contiguous()
 
 
-def _gpu_step(lib, case, kind, n, tgs=False):
+def _gpu_step(lib, case, kind, n, tgs=False, cap=None):
     """(result, team lanes, compact) of one mg_sim_simulate of the case's first n states; a second simulate from the
-    same states must be bit-identical"""
-    spec, sp = TP.spec_of(case), TP.sim_params(case, tgs)
+    same states must be bit-identical.  cap: max_contacts lowered below the case's"""
+    spec, sp = TP.spec_of(case), TP.sim_params(case, tgs, cap)
     mnp = M.pack_model(spec)
-    root, dof, act, _ = TP.states(case, kind, tgs)
+    root, dof, act, _ = TP.states(case, kind, tgs, cap)
     sim = C.c_void_p()
     _abi.check(lib.mg_sim_create(mnp.ctypes.data, C.byref(sp), n, 0, C.byref(sim)), lib)
     runs = []
@@ -115,3 +116,36 @@ def test_tree_tgs_physics_step_matches_oracle(lib, name):
     pgs = TP.pgs_step_of_tgs_states(case, "dropped")
     assert np.abs(got.dof[..., 1] - pgs.dof[..., 1]).max() > 1e-2   # the TGS kernel ran: PGS ends elsewhere
     TP.compare(f"test_tree_tgs_physics_step_matches_oracle[{name}]", case, "dropped", TP.CASE_ACTORS, got, tgs=True)
+
+
+# ------------------------------------------------------------------------------------------------ past capacity
+# More contact candidates than max_contacts: collide() keeps the first cap = min(max_contacts, MC) of the emission
+# order, as the oracle does.  The overflow states have max_contacts = MC, so slot cap is the first one past the
+# per-team contact arrays in LDS; the lowered runs take the max_contacts < MC branch.  The rows, PGS / TGS, sensors,
+# DOF forces and net contact forces all run on a full list.  tests/test_tree_physics_host.py asserts that the cut
+# matters to the oracle itself in at least half of the overflow states.
+@pytest.mark.parametrize("n", TP.ACTOR_COUNTS)
+@pytest.mark.parametrize("name", TP.OVERFLOW_CASES)
+def test_tree_overflow_step_matches_oracle(lib, name, n):
+    case = TP.CASES[name]
+    got, lanes, compact = _gpu_step(lib, case, "overflow", n)
+    _assert_instance(case, lanes, compact)
+    TP.compare(f"test_tree_overflow_step_matches_oracle[{name}-{n}]", case, "overflow", n, got)
+
+
+@pytest.mark.parametrize("n", TP.ACTOR_COUNTS)
+@pytest.mark.parametrize("name,cap", TP.LOWERED)
+def test_tree_lowered_capacity_step_matches_oracle(lib, name, cap, n):
+    case = TP.CASES[name]
+    got, lanes, compact = _gpu_step(lib, case, "dropped", n, cap=cap)
+    _assert_instance(case, lanes, compact)
+    TP.compare(f"test_tree_lowered_capacity_step_matches_oracle[{name}-{cap}-{n}]", case, "dropped", n, got, cap=cap)
+
+
+def test_tree_tgs_overflow_step_matches_oracle(lib):
+    case = TP.CASES["T32-free"]
+    got, lanes, compact = _gpu_step(lib, case, "overflow", TP.CASE_ACTORS, tgs=True)
+    _assert_instance(case, lanes, compact)
+    pgs = TP.pgs_step_of_tgs_states(case, "overflow")
+    assert np.abs(got.dof[..., 1] - pgs.dof[..., 1]).max() > 1e-2   # the TGS kernel ran: PGS ends elsewhere
+    TP.compare("test_tree_tgs_overflow_step_matches_oracle", case, "overflow", TP.CASE_ACTORS, got, tgs=True)

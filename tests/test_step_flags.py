@@ -108,3 +108,64 @@ def test_flags_quiet_in_calm_free_flight(task):
     np.testing.assert_allclose(d32[..., 0], d64[..., 0], atol=2e-4)
     np.testing.assert_allclose(r32[:, 7:13], r64[:, 7:13], atol=2e-3, rtol=2e-3)
     np.testing.assert_allclose(d32[..., 1], d64[..., 1], atol=2e-3, rtol=2e-3)
+
+
+# ------------------------------------------------------------------------------------------------ bit 128
+def _band_state(side):
+    """a T16-free dropped state moved in z so that its shallowest ground candidate stands half of STEP_DELTA below
+    (side = -1) or above (side = +1) the contact offset: (mnp, sp, state, position of that candidate in the list
+    with the thresholds moved out, the length of that list).  The candidate is neither first nor last."""
+    import tree_physics_ref as TP
+    case = TP.CASES["T16-free"]
+    spec, sp = TP.spec_of(case), TP.sim_params(case)
+    mnp = M.pack_model(spec)
+    wide = copy.copy(sp)
+    wide.contact_offset = sp.contact_offset + PS.STEP_DELTA
+    root, dof, act, _ = TP.states(case, "dropped")
+    for a in range(len(root)):
+        c = O.contacts_full(mnp, sp, root[a], dof[a], 64)
+        ground = np.flatnonzero(c[:, 2] < 0)
+        if len(ground) < 3:
+            continue
+        j = ground[np.argmax(c[ground, 10])]
+        r = root[a].copy()
+        r[2] += sp.contact_offset + side * 0.5 * PS.STEP_DELTA - c[j, 10]
+        cw = O.contacts_full(mnp, wide, r, dof[a], 64)
+        near = np.flatnonzero(np.abs(cw[:, 10] - sp.contact_offset) < PS.STEP_DELTA)
+        if len(near) != 1 or not 0 < near[0] < len(cw) - 1:
+            continue
+        assert (cw[near[0], 10] < sp.contact_offset) == (side < 0)
+        return mnp, sp, TP.TreeHost(spec, r[None], dof[a:a + 1], act[a:a + 1]), int(near[0]), len(cw)
+    raise AssertionError("no dropped state with a ground candidate between two others")
+
+
+@pytest.mark.parametrize("side", [-1, 1])
+def test_cut_near_a_threshold_sets_bit_128(side):
+    """known answers of bit 128: a candidate within STEP_DELTA of its threshold (either side) that stands before the
+    cut sets it, used or not; the same candidate behind the cut does not; nor does the same state with capacity to
+    spare, where bit 128 is unreachable"""
+    mnp, sp, pre, pos, total = _band_state(side)
+
+    def flags(k):
+        spk = copy.copy(sp)
+        spk.max_contacts = k
+        return int(PS.step_flags(mnp, spk, pre)[0])
+
+    assert flags(pos + 1) & 128        # the cut right behind the candidate: with it, the next one is dropped
+    assert flags(total - 1) & 128      # the cut at the last entry of the widened list
+    assert not flags(pos) & 128        # `pos` firm entries fill the list before the candidate is reached
+    assert not flags(1) & 128
+    assert not flags(total) & 128      # capacity to spare
+    assert not flags(sp.max_contacts) & 128 and total < sp.max_contacts
+
+
+def test_bit_128_is_unreachable_within_capacity():
+    """every tree state set chosen within capacity (dropped, settled) raises no bit 128"""
+    import tree_physics_ref as TP
+    for name in ("T16-fixed", "T32-free"):
+        case = TP.CASES[name]
+        spec, sp = TP.spec_of(case), TP.sim_params(case)
+        for kind in TP.KINDS:
+            root, dof, act, _ = TP.states(case, kind)
+            f = PS.step_flags(M.pack_model(spec), sp, TP.TreeHost(spec, root, dof, act))
+            assert not (f & 128).any()

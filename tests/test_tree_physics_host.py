@@ -8,6 +8,10 @@ same C in float, rounding unlike the kernel and unlike the fp64 checker) steps t
 the identical comparison (tree_physics_ref.compare).  It must end with no unexplained env and the flags within the
 cap, for every case, state kind and actor count the GPU test runs; the states' seeds and recipe
 (tree_physics_ref.states) were fixed against this test, never the rule.
+
+Past capacity (the overflow states, and the dropped states at a lowered max_contacts) the same holds, and two more
+conditions on the inputs are pinned: every overflow state has more candidates than max_contacts, and in at least
+half of them the cut moves the fp64 oracle's own result beyond the tolerances.
 """
 import numpy as np
 import pytest
@@ -18,9 +22,9 @@ import tree_physics_ref as TP
 from migym import model as M
 
 
-def _twin(case, kind, n, tgs=False):
-    spec, sp = TP.spec_of(case), TP.sim_params(case, tgs)
-    root, dof, act, _ = TP.states(case, kind, tgs)
+def _twin(case, kind, n, tgs=False, cap=None):
+    spec, sp = TP.spec_of(case), TP.sim_params(case, tgs, cap)
+    root, dof, act, _ = TP.states(case, kind, tgs, cap)
     return TP.TreeHost(spec, root[:n], dof[:n], act[:n]).simulate(M.pack_model(spec), sp, fp32=True)
 
 
@@ -44,6 +48,70 @@ def test_fp32_twin_tgs_step_matches_oracle(name):
     assert rec["unexplained"] == 0 and rec["flagged_reach"] <= PS.REACH_CAP
     # the solver really is another one: the same states under PGS end elsewhere
     assert np.abs(got.dof[..., 1] - TP.pgs_step_of_tgs_states(case, "dropped").dof[..., 1]).max() > 1e-2
+
+
+# ------------------------------------------------------------------------------------------------ past capacity
+@pytest.mark.parametrize("n", TP.ACTOR_COUNTS)
+@pytest.mark.parametrize("name", TP.OVERFLOW_CASES)
+def test_fp32_twin_overflow_step_matches_oracle(name, n):
+    """more candidates than max_contacts = the instance's MC: the twin keeps the oracle's prefix of the list"""
+    case = TP.CASES[name]
+    got = _twin(case, "overflow", n)
+    rec = TP.compare(f"test_fp32_twin_overflow_step_matches_oracle[{name}-{n}]", case, "overflow", n, got)
+    assert rec["unexplained"] == 0 and rec["flagged_reach"] <= PS.REACH_CAP
+
+
+@pytest.mark.parametrize("n", TP.ACTOR_COUNTS)
+@pytest.mark.parametrize("name,cap", TP.LOWERED)
+def test_fp32_twin_lowered_capacity_step_matches_oracle(name, cap, n):
+    """the dropped states with max_contacts lowered below the instance's MC"""
+    case = TP.CASES[name]
+    got = _twin(case, "dropped", n, cap=cap)
+    rec = TP.compare(f"test_fp32_twin_lowered_capacity_step_matches_oracle[{name}-{cap}-{n}]", case, "dropped", n, got,
+                     cap=cap)
+    assert rec["unexplained"] == 0 and rec["flagged_reach"] <= PS.REACH_CAP
+
+
+def test_fp32_twin_tgs_overflow_step_matches_oracle():
+    case = TP.CASES["T32-free"]
+    got = _twin(case, "overflow", TP.CASE_ACTORS, tgs=True)
+    rec = TP.compare("test_fp32_twin_tgs_overflow_step_matches_oracle", case, "overflow", TP.CASE_ACTORS, got, tgs=True)
+    assert rec["unexplained"] == 0 and rec["flagged_reach"] <= PS.REACH_CAP
+    assert np.abs(got.dof[..., 1] - TP.pgs_step_of_tgs_states(case, "overflow").dof[..., 1]).max() > 1e-2
+    assert 2 * TP.truncation_moves(case, "overflow", tgs=True).sum() >= TP.CASE_ACTORS
+
+
+def _record_counts(key, before, cap, moves):
+    PS._REPORT.setdefault(key, {})["counts"] = {"over_capacity": int((before > cap).sum()), "most": int(before.max()),
+                                                "cut_moves_oracle": int(moves.sum())}
+
+
+@pytest.mark.parametrize("name", TP.OVERFLOW_CASES)
+def test_overflow_states_are_past_capacity_and_the_cut_matters(name):
+    """every overflow state has more candidates than max_contacts (= the instance's MC) and fewer than the oracle can
+    count; in at least half of them the fp64 oracle's own step with room for every candidate leaves the tolerances
+    of its step at capacity, so a kernel that ignored the cut would fail"""
+    case = TP.CASES[name]
+    before = TP.candidates_before(case, "overflow")
+    assert len(before) == TP.CASE_ACTORS
+    assert before.min() > case.max_contacts and before.max() < TP.ORACLE_MAXC, (before.min(), before.max())
+    moves = TP.truncation_moves(case, "overflow")
+    _record_counts(f"overflow inputs[{name}]", before, case.max_contacts, moves)
+    assert 2 * moves.sum() >= TP.CASE_ACTORS, f"{name}: the cut matters to the oracle in only {moves.sum()} states"
+
+
+# (envs over the lowered capacity, envs where the cut moves the oracle's result): pinned, the states are seeded
+LOWERED_COUNTS = {("T16-fixed", 8): (17, 17), ("T32-free", 8): (22, 19)}
+
+
+@pytest.mark.parametrize("name,cap", TP.LOWERED)
+def test_lowered_capacity_cuts_the_dropped_states(name, cap):
+    case = TP.CASES[name]
+    before = TP.candidates_before(case, "dropped")
+    moves = TP.truncation_moves(case, "dropped", cap=cap)
+    _record_counts(f"overflow inputs[{name}-{cap}]", before, cap, moves)
+    assert not moves[before <= cap].any()   # a list that fits is left alone
+    assert (int((before > cap).sum()), int(moves.sum())) == LOWERED_COUNTS[name, cap]
 
 
 @pytest.mark.parametrize("name", list(TP.CASES))

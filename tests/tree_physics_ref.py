@@ -4,23 +4,47 @@ the comparison, shared by tests/test_gpu_tree_physics.py (the GPU against the or
 tests/test_tree_physics_host.py (the oracle's fp32 twin against it, through the same rule).
 
 A case is a dynamics_ref.random_tree with gravity, joint damping / stiffness / frictionloss, ground geoms, self pairs
-and sensors, and two kinds of states of CASE_ACTORS actors:
+and sensors, and three kinds of states of CASE_ACTORS actors:
 
   * dropped: a random base pose with the lowest geom point U(-3, 3) cm from the plane, q in U(-1.05, 1.05) (limits
     are +-1, the limit margin 0.1: a third of the joints carry a limit row), qd ~ N(0, 1), the base twist ~ N(0, 0.5)
     when the base is free, effort actuation in U(-2, 2);
-  * settled: the dropped states rolled SETTLE_STEPS steps by the fp64 oracle, so that contacts rest.
+  * settled: the dropped states rolled SETTLE_STEPS steps by the fp64 oracle, so that contacts rest;
+  * overflow (OVERFLOW_CASES): drawn like dropped, then every actor sunk a centimetre at a time, SINK_STEPS at most,
+    until the fp64 oracle counts more contact candidates than max_contacts.  max_contacts is the instance's MC (24 or
+    48), so collide() cuts the list at the last slot of the per-team arrays and the step runs on a full list.
 
 On the 16- and 32-lane cases every fourth dropped actor is lowered further, until it has more contact candidates than
 the team has lanes (dropped_pool); the settled states roll from the pool without that.
 
 States are drawn into a pool and taken in pool order under conditions on the INPUTS, all decided by the fp64
 oracle alone: the contact candidates of the state and of the oracle's state after the step stay at or below
-max_contacts (what happens past capacity is a separate question), no self pair overlaps by more than
+max_contacts (overflow turns this round: more than max_contacts and fewer than ORACLE_MAXC = 64 before the step, the
+most the oracle can count), no self pair overlaps by more than
 PAIR_DEPTH (3 cm, as deep as the lowest geom may stand in the ground: a 40-link chain thrown apart at the
 depenetration speed is a stress state, where the oracle's own fp32 build leaves the tolerances), the oracle's step
 is not sensitive to SENS_EPS on the positions, and the first SMALL_N actors' steps pass no discontinuity (orc_step_flips == 0): the batches of 1 and 6 actors are prefixes of the 66, and a single
 flagged env of 6 would already be 17 % of them, past the 5 % the exemption rule may reach.
+
+Past capacity two more things hold.  The overflow states are also chosen so that the cut matters: at most half of
+them may be states where the oracle's step with room for every candidate (max_contacts = 64) stays within the
+tolerances of its step at capacity; past that such a state is passed over in pool order (it changes the selection of
+T16-free alone, whose free base rests on 24 redundant ground contacts: 17 of its first 66 usable states feel the
+cut).  truncation_moves() recomputes that, and tests/test_tree_physics_host.py asserts at least half.  And the
+dropped states of LOWERED run once more with max_contacts = 8 (states(..., cap=8): the same states, the oracle's step
+recomputed at that capacity), the p->max_contacts < MC branch.
+
+The fixed bases and the sink depth.  A fixed-base tree cannot rise out of the ground, so a sunk one is a stress state
+(contact forces 1e6-1e12 N, most hinge rates at the 64 rad/s cap).  The fp32 twin on the whole pools (264 actors per
+case, no filter): no env leaves the tolerances on T16-fixed and T32-fixed at any depth up to 60 cm; 2 of 144
+past-capacity actors do on T16-fixed-round (39 and 40 cm), 4 of 114 on T64-fixed (28-48 cm), 20 of 134 on
+T64-fixed-chain (from 24 cm), each 1.1-18 x the velocity tolerance and none flagged.  They do not gather at the deep
+end, and a bound that excludes them leaves too few states: the pool yields 66 usable states only from 42 cm
+(T16-fixed-round), 60 cm (T32-fixed), 50 cm (T64-fixed) and 42 cm (T64-fixed-chain) on.  So SINK_STEPS_FIXED stays at
+the 60 cm of SINK_STEPS; T64-fixed and T64-fixed-chain are left out of OVERFLOW_CASES (the twin leaves the rule in 4
+and 6 of their 66 states); and T16-fixed-round draws its overflow pool from overflow_seed = state_seed + 1000, the
+first of state_seed + 1000 k at which the twin stays within the rule (at state_seed itself actor 2 is 1.96 x outside
+the velocity tolerance, unflagged).
 """
 import dataclasses
 
@@ -47,6 +71,7 @@ class Case:
     # what puts the case past the next smaller instance (asserted on the spec): each a (count name, more than)
     past: tuple
     reaches: tuple         # the paths its inputs must reach (asserted on the host): see reach_report
+    overflow_seed: int = None   # the overflow pool's seed where state_seed's draw leaves the twin's rule
 
     def name(self):
         return (f"T{self.lanes}-{'free' if self.tree.get('free_base') else 'fixed'}"
@@ -65,7 +90,7 @@ CASES = {c.name(): c for c in (
          ("box", "cand>T", "pair", "limit", "geoms>T")),
     # spheres and capsules alone take the one-pass ground loop (team_physics.hpp collide, ground_round): its second round
     Case(16, _tree(12, 1, num_geoms=20, num_pairs=8, boxes=False), 24, 108, (("nodes", 9), ("geoms", 16), ("pairs", 0)),
-         ("cand>T", "pair", "limit", "geoms>T")),
+         ("cand>T", "pair", "limit", "geoms>T"), overflow_seed=1108),
     Case(16, _tree(10, 1, num_geoms=18, num_pairs=8, free_base=True), 24, 102, (("nodes", 9), ("geoms", 16)),
          ("box", "cand>T", "pair", "limit", "geoms>T")),
     Case(32, _tree(30, 1, num_geoms=40, num_pairs=170), 48, 103, (("nodes", 24), ("geoms", 24), ("pairs", 160)),
@@ -79,6 +104,13 @@ CASES = {c.name(): c for c in (
          ("box", "pair", "limit")),
 )}
 KINDS = ("dropped", "settled")
+# past capacity (module docstring): the cases whose pool yields CASE_ACTORS usable overflow states, and the lowered
+# capacity the dropped states of two of them also run at (the p->max_contacts < MC branch of collide())
+OVERFLOW_CASES = ("T16-fixed", "T16-fixed-round", "T16-free", "T32-fixed", "T32-free", "T64-free")
+LOWERED = (("T16-fixed", 8), ("T32-free", 8))
+SINK_STEPS = 60          # an actor sinks a centimetre at a time, at most this far (as dropped_pool)
+SINK_STEPS_FIXED = 60    # ... and a fixed-base tree at most this far: no tighter bound helps (module docstring)
+ORACLE_MAXC = 64         # the oracle's own list ends here: it cannot count a state with this many candidates
 _cache = {}
 
 
@@ -93,8 +125,9 @@ def counts(spec):
                 lanes=max((0 if spec.fixed_base else 6) + spec.num_dofs, len(spec.sensors)))
 
 
-def sim_params(case, tgs=False):
-    sp = taskdefs.sim_params(configs.task_config("Ant", 16), case.max_contacts)
+def sim_params(case, tgs=False, cap=None):
+    """cap: a lowered max_contacts (None: the case's, which equals its instance's MC)"""
+    sp = taskdefs.sim_params(configs.task_config("Ant", 16), case.max_contacts if cap is None else cap)
     if tgs:
         sp.solver_type = _abi.MG_SOLVER_TGS
     return sp
@@ -172,6 +205,20 @@ def dropped_pool(spec, mnp, sp, lanes, n, seed, sink=True):
     return root, dof, act
 
 
+def overflow_pool(spec, mnp, sp, n, seed):
+    """the dropped pool (no actor lowered for "cand>T"), then every actor sunk a centimetre at a time until the fp64
+    oracle counts more than max_contacts candidates, SINK_STEPS cm at most (SINK_STEPS_FIXED for a fixed base, which
+    cannot rise out of the ground: see the comment in dropped_pool); an actor that never gets there stays in the
+    pool and fails the capacity condition of states()"""
+    root, dof, act = dropped_pool(spec, mnp, sp, 0, n, seed, sink=False)
+    for a in range(n):
+        for _ in range(SINK_STEPS_FIXED if spec.fixed_base else SINK_STEPS):
+            if len(O.contacts(mnp, sp, root[a], dof[a], ORACLE_MAXC)) > sp.max_contacts:
+                break
+            root[a, 2] -= 0.01
+    return root, dof, act
+
+
 SENS_EPS = 1e-6      # parity_stats.simulate_sensitive's perturbation
 PAIR_DEPTH = 0.03    # a self pair may overlap as far as the lowest geom may stand in the ground
 
@@ -185,15 +232,23 @@ def num_candidates(mnp, sp, root, dof):
     return out
 
 
-def states(case, kind, tgs=False):
+def states(case, kind, tgs=False, cap=None):
     """(root, dof, act, host64): CASE_ACTORS actors' states before the step, read-only, and the fp64 oracle's TreeHost
-    after one simulate from them; computed once per (case, kind, solver)"""
-    key = ("states", case.name(), kind, tgs)
+    after one simulate from them; computed once per (case, kind, solver, capacity).  cap: the states chosen at the
+    case's own capacity, with the oracle's step recomputed at max_contacts = cap"""
+    key = ("states", case.name(), kind, tgs, cap)
     if key in _cache:
         return _cache[key]
     spec, sp = spec_of(case), sim_params(case, tgs)
     mnp = M.pack_model(spec)
-    root, dof, act = dropped_pool(spec, mnp, sp, case.lanes, POOL, case.state_seed, sink=kind == "dropped")
+    if cap is not None:
+        root, dof, act, _ = states(case, kind, tgs)
+        _cache[key] = root, dof, act, TreeHost(spec, root, dof, act).simulate(mnp, sim_params(case, tgs, cap))
+        return _cache[key]
+    if kind == "overflow":
+        root, dof, act = overflow_pool(spec, mnp, sp, POOL, case.overflow_seed or case.state_seed)
+    else:
+        root, dof, act = dropped_pool(spec, mnp, sp, case.lanes, POOL, case.state_seed, sink=kind == "dropped")
     if kind == "settled":
         h = TreeHost(spec, root, dof, act)
         for _ in range(SETTLE_STEPS):
@@ -203,8 +258,11 @@ def states(case, kind, tgs=False):
         root, dof, act = root[ok], dof[ok], act[ok]
     after = TreeHost(spec, root, dof, act).simulate(mnp, sp)
     before = num_candidates(mnp, sp, root, dof)
-    fits = (before >= 0) & (before <= case.max_contacts) & \
-        (np.abs(num_candidates(mnp, sp, after.root, after.dof)) <= case.max_contacts)
+    if kind == "overflow":   # the capacity condition turned round: past it, and countable by the oracle
+        fits = (before > case.max_contacts) & (before < ORACLE_MAXC)
+    else:
+        fits = (before >= 0) & (before <= case.max_contacts) & \
+            (np.abs(num_candidates(mnp, sp, after.root, after.dof)) <= case.max_contacts)
     # ... and the oracle's own step is not sensitive there: with every position moved by +-SENS_EPS (an fp32 step's
     # rounding; one draw of the signs), its result stays within a quarter of the tolerances
     n = len(root)
@@ -219,8 +277,19 @@ def states(case, kind, tgs=False):
               PS.env_bad(moved.root[:, 7:13], after.root[:, 7:13], 0.25 * 2e-3, 0.25 * 2e-3))
     _cache["pool", case.name(), kind, tgs] = (n, int(fits.sum()))
     flags = O.step_flips(mnp, sp, TreeHost(spec, root, dof, act), PS.STEP_DELTA, PS.STEP_DF)
+    # overflow: at most half of the states may be ones where the cut does not matter to the oracle itself (its step
+    # with room for every candidate stays within the tolerances of its step at capacity): past that, such a state is
+    # passed over, so that a kernel that ignored the cut could not pass
+    inert = np.zeros(n, bool)
+    if kind == "overflow":
+        roomy = TreeHost(spec, root, dof, act).simulate(mnp, sim_params(case, tgs, ORACLE_MAXC))
+        inert[:] = True
+        for _, a, b, atol, rtol in outside(roomy, after, n):
+            inert &= ~PS.env_bad(a, b, atol, rtol)
     keep = []
     for a in np.flatnonzero(fits):
+        if inert[a] and inert[keep].sum() >= CASE_ACTORS // 2:
+            continue
         if len(keep) >= SMALL_N or flags[a] == 0:
             keep.append(a)
         if len(keep) == CASE_ACTORS:
@@ -265,16 +334,46 @@ def reach_report(case, kind, tgs=False):
 
 
 # ------------------------------------------------------------------------------------------------ the comparison
-def compare(test, case, kind, n, got, tgs=False, reach_cap=PS.REACH_CAP):
+def outside(got, ref, n):
+    """[(name, got, ref, atol, rtol)] of the one-step tolerances, the references cut to the first n envs"""
+    f_h, s_h, c_h = ref.dof_force[:n], ref.sensors[:n], ref.ncf[:n]
+    return [("root pose", got.root[:, 0:7], ref.root[:n, 0:7], 2e-4, 0),
+            ("dof pos", got.dof[..., 0], ref.dof[:n, :, 0], 2e-4, 0),
+            ("root twist", got.root[:, 7:13], ref.root[:n, 7:13], 2e-3, 2e-3),
+            ("dof vel", got.dof[..., 1], ref.dof[:n, :, 1], 2e-3, 2e-3),
+            ("dof force", got.dof_force, f_h, 1e-2 * max(1.0, np.abs(f_h).max()), 0),
+            ("sensors", got.sensors, s_h, 1e-2 * max(1.0, np.abs(s_h).max()), 0),
+            ("net contact forces", got.ncf, c_h, 1e-2 * max(1.0, np.abs(c_h).max()), 0)]
+
+
+def truncation_moves(case, kind, tgs=False, cap=None):
+    """per env: the fp64 oracle's step with room for every candidate (max_contacts = ORACLE_MAXC) leaves the one-step
+    tolerances of its step at the capacity under test -- the cut changes the result there, so an implementation that
+    ignored it would be caught"""
+    spec = spec_of(case)
+    root, dof, act, ref = states(case, kind, tgs, cap)
+    roomy = TreeHost(spec, root, dof, act).simulate(M.pack_model(spec), sim_params(case, tgs, ORACLE_MAXC))
+    bad = np.zeros(len(root), bool)
+    for _, a, b, atol, rtol in outside(roomy, ref, len(root)):
+        bad |= PS.env_bad(a, b, atol, rtol)
+    return bad
+
+
+def candidates_before(case, kind, tgs=False):
+    """per env: the fp64 oracle's count of contact candidates before the step (at most ORACLE_MAXC)"""
+    spec = spec_of(case)
+    root, dof, act, _ = states(case, kind, tgs)
+    return np.abs(num_candidates(M.pack_model(spec), sim_params(case, tgs), root, dof))
+
+
+def compare(test, case, kind, n, got, tgs=False, reach_cap=PS.REACH_CAP, cap=None):
     """`got`: a TreeHost-like result (root, dof, sensors, dof_force, ncf) of one simulate of the case's first n states
     by the implementation under test.  Every env within the one-step tolerances of the fp64 oracle (positions 2e-4,
     velocities 2e-3 + 2e-3 |v|, DOF forces / sensors / net contact forces 1 % of the batch's largest), unless
     orc_step_flips puts its step at a discontinuity (parity_stats.assert_steps_explained: reach at most 5 %, no
     sensitivity fallback, nothing unexplained); finite; and the states moved.  Returns the exemption record."""
-    spec, sp = spec_of(case), sim_params(case, tgs)
-    root, dof, act, ref = states(case, kind, tgs)
-    r_h, d_h = ref.root[:n], ref.dof[:n]
-    s_h, f_h, c_h = ref.sensors[:n], ref.dof_force[:n], ref.ncf[:n]
+    spec, sp = spec_of(case), sim_params(case, tgs, cap)
+    root, dof, act, ref = states(case, kind, tgs, cap)
     for x in (got.root, got.dof, got.sensors, got.dof_force, got.ncf):
         assert np.isfinite(x).all()
     assert np.abs(got.dof[..., 0] - dof[:n, :, 0]).max() > 1e-3, "the step moved nothing"
@@ -282,14 +381,8 @@ def compare(test, case, kind, n, got, tgs=False, reach_cap=PS.REACH_CAP):
         np.testing.assert_array_equal(got.root, root[:n])   # a fixed root is left as it was
     else:
         assert np.abs(got.root[:, 0:3] - root[:n, 0:3]).max() > 1e-3
-    checks = [("root pose", got.root[:, 0:7], r_h[:, 0:7], 2e-4, 0), ("dof pos", got.dof[..., 0], d_h[..., 0], 2e-4, 0),
-              ("root twist", got.root[:, 7:13], r_h[:, 7:13], 2e-3, 2e-3),
-              ("dof vel", got.dof[..., 1], d_h[..., 1], 2e-3, 2e-3),
-              ("dof force", got.dof_force, f_h, 1e-2 * max(1.0, np.abs(f_h).max()), 0),
-              ("sensors", got.sensors, s_h, 1e-2 * max(1.0, np.abs(s_h).max()), 0),
-              ("net contact forces", got.ncf, c_h, 1e-2 * max(1.0, np.abs(c_h).max()), 0)]
     bad = np.zeros(n, bool)
-    for name, a, b, atol, rtol in checks:
+    for name, a, b, atol, rtol in outside(got, ref, n):
         eb = PS.env_bad(a, b, atol, rtol)
         PS.record(test, name, a, b, envs_outside=int(eb.sum()), atol=atol, rtol=rtol)
         bad |= eb
