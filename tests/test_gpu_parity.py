@@ -21,6 +21,7 @@ import torch
 import parity_stats as PS
 import pyoracle as O
 from migym import _abi, configs, model as M, taskdefs
+from simparams_ref import random_states   # the physics tests' random states (shared with the CPU tests)
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -207,23 +208,6 @@ def test_device_rng_equals_oracle_rng(lib):
 
 
 # -------------------------------------------------------------------------------------- physics
-def random_states(spec, tp, n, rng, z_range, contact_frac=0.5):
-    nd = spec.num_dofs
-    root = np.zeros((n, 13), np.float32)
-    root[:, 0:2] = rng.uniform(-2, 2, (n, 2))
-    root[:, 2] = rng.uniform(*z_range, n)
-    yaw = rng.uniform(-np.pi, np.pi, n)
-    tilt = rng.normal(0, 0.3, (n, 2))
-    q = np.stack([tilt[:, 0] * 0.5, tilt[:, 1] * 0.5, np.sin(yaw / 2), np.cos(yaw / 2)], -1)
-    root[:, 3:7] = q / np.linalg.norm(q, axis=-1, keepdims=True)
-    root[:, 7:13] = rng.normal(0, 0.5, (n, 6))
-    lo, hi = np.array(tp.dof_lower[:nd]), np.array(tp.dof_upper[:nd])
-    dof = np.zeros((n, nd, 2), np.float32)
-    dof[:, :, 0] = lo + (hi - lo) * rng.uniform(-0.05, 1.05, (n, nd))
-    dof[:, :, 1] = rng.normal(0, 1.0, (n, nd))
-    return root, dof
-
-
 def _gpu_simulate(lib, mnp, sp, root, dof, act, ns):
     """one mg_sim_simulate of the states on the device: (root, dof, sensors, dof force) after it"""
     n = len(root)

@@ -32,6 +32,11 @@ unless orc_step_flips puts its step at a discontinuity, flags reaching at most 5
 fallback, nothing unexplained (tree_physics_ref.compare); a second run bit-identical; outputs finite; the states
 moved.  tests/test_tree_physics_host.py puts the oracle's fp32 twin through the same comparison on the CPU, and
 asserts what the inputs reach.
+
+All of this runs at one point of mg_sim_params, the Ant's (tree_physics_ref.sim_params).  tests/test_gpu_simparams.py
+takes T16-free, T32-fixed and T64-free (dropped states) to twelve other points -- substeps, tilted gravity, low and zero
+friction, the depenetration clamp, rest_offset, 1 and 16 iterations, limit_margin 0, baumgarte, TGS with vel_iters --
+through the same comparison (tree_physics_ref.compare(point=...)).
 """
 import ctypes as C
 import types

@@ -540,3 +540,172 @@ def test_frictionloss_decelerates_then_creeps():
     for _ in range(200):
         O.simulate(mnp, sp, root, dof, act)
     np.testing.assert_allclose(dof[0, 0, 1], 0.01 * np.arctanh(0.5), rtol=1e-3)
+
+
+# ------------------------------------------------------------------ sim parameters away from the tasks' values
+# Known answers of the branches that read mg_sim_params fields no task YAML moves (tests/simparams_ref.py): the
+# oracle is what the kernels are held to at those points, so each law is pinned here on the fp64 build and on its
+# fp32 twin (at fp32 tolerance).
+BUILDS = pytest.mark.parametrize("fp32", [False, True], ids=["fp64", "fp32"])
+
+
+def _tol(fp32, t64, t32):
+    return t32 if fp32 else t64
+
+
+def one_body_spec(geom=None, size=None, mass=1.0, inertia=(0.02, 0.02, 0.02)):
+    """one free rigid body (no link damping, no angular-velocity cap) carrying at most one geom at its COM"""
+    spec = free_link_spec(0.0, 0.0, inertia)
+    spec.nodes[0].mass = spec.bodies[0].mass = mass
+    if geom is not None:
+        spec.geoms.append(M.Geom(name="g", gtype=geom, node=0, body=0, size=list(size), pos=[0, 0, 0],
+                                 quat=[0, 0, 0, 1]))
+    return spec
+
+
+def _params(substeps=1, gravity=(0.0, 0.0, 0.0), max_contacts=8, **over):
+    """the Ant's sim params with one substep of its h = 1 / 120 s (or `substeps` of them)"""
+    sp = taskdefs.sim_params(configs.task_config("Ant", 1), max_contacts)
+    sp.dt, sp.substeps = sp.dt / sp.substeps * substeps, substeps
+    for i in range(3):
+        sp.gravity[i] = gravity[i]
+    for k, v in over.items():
+        setattr(sp, k, v)
+    return sp
+
+
+def _free_root(pos, vel=(0, 0, 0), w=(0, 0, 0)):
+    root = np.zeros((1, 13), np.float32)
+    root[0, 0:3], root[0, 6], root[0, 7:10], root[0, 10:13] = pos, 1.0, vel, w
+    return root
+
+
+NO_DOF = np.zeros((1, 0, 2), np.float32)
+
+
+@BUILDS
+@pytest.mark.parametrize("n", [1, 3, 4])
+def test_tilted_gravity_free_flight(n, fp32):
+    """a free body in flight under g = (3, -2, -8): v' = v + g dt, x' = x + v dt + g h^2 n (n + 1) / 2 over the n
+    substeps of one step, in every component"""
+    g = np.array([3.0, -2.0, -8.0])
+    sp = _params(substeps=n, gravity=g)
+    x0, v0 = np.array([0.5, -0.25, 3.0]), np.array([0.3, -0.2, 0.1])
+    root = _free_root(x0, v0)   # no spin: the integrator's w x dp term turns the velocity of a spinning body
+    O.simulate(M.pack_model(one_body_spec()), sp, root, NO_DOF, fp32=fp32)
+    h = sp.dt / n
+    np.testing.assert_allclose(root[0, 7:10], v0 + g * sp.dt, rtol=0, atol=_tol(fp32, 2e-7, 2e-6))
+    np.testing.assert_allclose(root[0, 0:3], x0 + v0 * sp.dt + g * h * h * n * (n + 1) / 2, rtol=0,
+                               atol=_tol(fp32, 3e-7, 2e-6))
+    assert not root[0, 10:13].any()
+
+
+def _flat_box(u, mu, fp32, iters=64):
+    """a 1 x 1 x 0.02 m box of 1 kg lying flat on the plane (gap 0), sliding along x at u: (vx, vy, vz, |w|, sp)
+    after one step of two substeps; `iters` sweeps, so that PGS converges on the four redundant corner contacts"""
+    a, b, c = 0.5, 0.5, 0.01
+    I = [(b * b + c * c) / 3, (a * a + c * c) / 3, (a * a + b * b) / 3]
+    spec = one_body_spec(M.GT_BOX, (a, b, c), 1.0, I)
+    sp = _params(substeps=2, gravity=(0.0, 0.0, -9.81), friction=mu, pos_iters=iters)
+    root = _free_root((0.0, 0.0, c), (u, 0.0, 0.0))
+    O.simulate(M.pack_model(spec), sp, root, NO_DOF, fp32=fp32)
+    return root[0, 7], root[0, 8], root[0, 9], np.abs(root[0, 10:13]).max(), sp
+
+
+@BUILDS
+def test_friction_bound_known_answers(fp32):
+    """the friction bound |lam_t| <= mu lam_n: the normal impulses of a box at rest on the plane carry m |g_z| h per
+    substep, so sliding at mu = 0.2 loses mu |g_z| dt of its speed per step; at mu = 0 (the bound [-0, 0]) none; and
+    at mu = 1 a box slower than |g_z| dt stops"""
+    tol = _tol(fp32, 1e-6, 2e-5)
+    u = 1.0
+    vx, vy, vz, w, sp = _flat_box(u, 0.2, fp32)
+    assert abs((u - vx) - 0.2 * 9.81 * sp.dt) < tol, (u - vx, 0.2 * 9.81 * sp.dt)
+    assert abs(vy) < tol and abs(vz) < tol and w < 10 * tol
+    vx, vy, vz, w, sp = _flat_box(u, 0.0, fp32)
+    assert vx == np.float32(u) and abs(vy) < tol and abs(vz) < tol
+    u = 0.5 * 9.81 * sp.dt
+    vx, vy, vz, w, sp = _flat_box(u, 1.0, fp32)
+    assert abs(vx) < tol and abs(vy) < tol and abs(vz) < tol
+
+
+@BUILDS
+@pytest.mark.parametrize("tgs", [False, True], ids=["pgs", "tgs"])
+@pytest.mark.parametrize("d,vmax,rest", [(0.01, 10.0, 0.0), (0.01, 0.1, 0.0), (0.01, 10.0, 0.0025), (0.05, 0.3, 0.0025)])
+def test_depenetration_clamp_known_answer(d, vmax, rest, tgs, fp32):
+    """a sphere at rest sunk by d, zero gravity, one substep: the normal row's target is
+    min(baumgarte (d + rest_offset) / h, max_depen_vel), below and above the clamp.  PGS leaves at that velocity and
+    moves by h times it.  TGS applies the same rule per sub-step of h / N to the gap moved by the sub-steps so far
+    (e_k+1 = e_k + (h / N) min(-baumgarte e_k N / h, max_depen_vel)), moves by the sum of the sub-steps, and its
+    velocity sweeps take the depenetration velocity out again while the sphere still penetrates"""
+    r, bg, N = 0.125, 0.2, 4
+    sp = _params(max_depen_vel=vmax, rest_offset=rest, baumgarte=bg, pos_iters=N,
+                 solver_type=_abi_solver(tgs))
+    h = sp.dt
+    z0 = np.float32(r - d)
+    root = _free_root((0.0, 0.0, z0))
+    O.simulate(M.pack_model(one_body_spec(M.GT_SPHERE, (r,))), sp, root, NO_DOF, fp32=fp32)
+    e0 = (float(z0) - r) - float(np.float32(rest))
+    assert (bg * -e0 / h > vmax) == (vmax < 1.0)   # the cases stand on either side of the clamp
+    if not tgs:
+        v = min(bg * -e0 / h, vmax)
+        want_v, want_dz = v, h * v
+    else:
+        e, hs = e0, h / N
+        for _ in range(N):
+            e += hs * min(-bg * e / hs, vmax)
+        assert e < 0
+        want_v, want_dz = 0.0, e - e0
+    tol = _tol(fp32, 1e-6, 2e-5)
+    assert abs(root[0, 9] - want_v) < tol * max(1.0, abs(want_v)), (root[0, 9], want_v)
+    assert abs((root[0, 2] - float(z0)) - want_dz) < _tol(fp32, 1e-7, 1e-6), (root[0, 2] - float(z0), want_dz)
+    assert np.abs(root[0, 7:9]).max() == 0 and np.abs(root[0, 10:13]).max() == 0
+
+
+def _abi_solver(tgs):
+    from migym import _abi
+    return _abi.MG_SOLVER_TGS if tgs else _abi.MG_SOLVER_PGS
+
+
+@BUILDS
+def test_rest_offset_is_where_the_normal_row_turns_on(fp32):
+    """a sphere at rest at gap = rest_offset, zero gravity: no impulse (the row's target is 0 at zero speed); at gap
+    rest_offset - eps the Baumgarte term pushes it out at baumgarte eps / h.  Radius, offset and eps are powers of
+    two, so the gap is exact in both builds"""
+    r, rest, eps = 0.125, 2.0 ** -7, 2.0 ** -10
+    sp = _params(rest_offset=rest, contact_offset=0.02)
+    mnp = M.pack_model(one_body_spec(M.GT_SPHERE, (r,)))
+    root = _free_root((0.0, 0.0, r + rest))
+    O.simulate(mnp, sp, root, NO_DOF, fp32=fp32)
+    assert np.abs(root[0, 7:13]).max() == 0 and root[0, 2] == np.float32(r + rest)
+    root = _free_root((0.0, 0.0, r + rest - eps))
+    O.simulate(mnp, sp, root, NO_DOF, fp32=fp32)
+    np.testing.assert_allclose(root[0, 9], sp.baumgarte * eps / sp.dt, rtol=_tol(fp32, 1e-6, 1e-5))
+    # with rest_offset 0 the same state is a separated contact: no impulse
+    root = _free_root((0.0, 0.0, r + rest - eps))
+    O.simulate(mnp, _params(rest_offset=0.0, contact_offset=0.02), root, NO_DOF, fp32=fp32)
+    assert np.abs(root[0, 7:13]).max() == 0
+
+
+@BUILDS
+def test_limit_margin_zero_builds_no_speculative_row(fp32):
+    """a hinge 0.05 rad inside its upper limit moving toward it at 12 rad/s (0.1 rad per substep of 1 / 120 s): with limit_margin 0
+    no row is built and the joint crosses the limit; with the margin 0.1 the speculative row (target -d / h) stops
+    it at the limit"""
+    spec = hinge_link_spec(0.0)
+    spec.nodes[1].limited, spec.nodes[1].lower, spec.nodes[1].upper = 1, -1.0, 1.0
+    mnp = M.pack_model(spec)
+    root = np.zeros((1, 13), np.float32)
+    root[0, 6] = 1.0
+    got = {}
+    for margin in (0.0, 0.1):
+        sp = _params(limit_margin=margin, max_contacts=0)
+        dof = np.zeros((1, 1, 2), np.float32)
+        dof[0, 0] = (0.95, 12.0)
+        O.simulate(mnp, sp, root.copy(), dof, fp32=fp32)
+        got[margin] = dof[0, 0].astype(np.float64)
+    h = float(_params().dt)
+    tol = _tol(fp32, 1e-6, 1e-5)
+    assert abs(got[0.0][1] - 12.0) < tol and abs(got[0.0][0] - (0.95 + 12.0 * h)) < tol and got[0.0][0] > 1.0
+    d = 1.0 - float(np.float32(0.95))
+    assert abs(got[0.1][1] - d / h) < 100 * tol and abs(got[0.1][0] - 1.0) < tol

@@ -34,6 +34,10 @@ cut).  truncation_moves() recomputes that, and tests/test_tree_physics_host.py a
 dropped states of LOWERED run once more with max_contacts = 8 (states(..., cap=8): the same states, the oracle's step
 recomputed at that capacity), the p->max_contacts < MC branch.
 
+Every case stands at the Ant's sim parameters.  sim_params, states and compare take point=<a name of
+simparams_ref.POINTS> to move them (tests/test_gpu_simparams.py, tests/test_simparams_host.py): the states are chosen
+again at the point by the same rule, and point=None is the Ant's parameters and the states of before, bit for bit.
+
 The fixed bases and the sink depth.  A fixed-base tree cannot rise out of the ground, so a sunk one is a stress state
 (contact forces 1e6-1e12 N, most hinge rates at the 64 rad/s cap).  The fp32 twin on the whole pools (264 actors per
 case, no filter): no env leaves the tolerances on T16-fixed and T32-fixed at any depth up to 60 cm; 2 of 144
@@ -53,6 +57,7 @@ import numpy as np
 import dynamics_ref as D
 import parity_stats as PS
 import pyoracle as O
+import simparams_ref as SR
 from migym import _abi, configs, model as M, taskdefs
 
 CASE_ACTORS = 66      # 16 full waves of four 16-lane teams and a half-filled one; 33 waves of two; 66 of one
@@ -125,12 +130,13 @@ def counts(spec):
                 lanes=max((0 if spec.fixed_base else 6) + spec.num_dofs, len(spec.sensors)))
 
 
-def sim_params(case, tgs=False, cap=None):
-    """cap: a lowered max_contacts (None: the case's, which equals its instance's MC)"""
+def sim_params(case, tgs=False, cap=None, point=None):
+    """cap: a lowered max_contacts (None: the case's, which equals its instance's MC); point: a name of
+    simparams_ref.POINTS, the fields it sets replacing the Ant's (None: the Ant's own)"""
     sp = taskdefs.sim_params(configs.task_config("Ant", 16), case.max_contacts if cap is None else cap)
     if tgs:
         sp.solver_type = _abi.MG_SOLVER_TGS
-    return sp
+    return SR.apply(sp, point, case.name())
 
 
 class TreeHost:
@@ -232,23 +238,27 @@ def num_candidates(mnp, sp, root, dof):
     return out
 
 
-def states(case, kind, tgs=False, cap=None):
+def states(case, kind, tgs=False, cap=None, point=None):
     """(root, dof, act, host64): CASE_ACTORS actors' states before the step, read-only, and the fp64 oracle's TreeHost
-    after one simulate from them; computed once per (case, kind, solver, capacity).  cap: the states chosen at the
-    case's own capacity, with the oracle's step recomputed at max_contacts = cap"""
-    key = ("states", case.name(), kind, tgs, cap)
+    after one simulate from them; computed once per (case, kind, solver, capacity, point).  cap: the states chosen at
+    the case's own capacity, with the oracle's step recomputed at max_contacts = cap.  point: the sim parameters moved
+    to a point of simparams_ref.POINTS; the states are chosen again there by the same rule (candidates, flags and
+    sensitivity all depend on the parameters), from the pool of state_seed + 1000 k where the admission rule took
+    the k-th next seed"""
+    key = ("states", case.name(), kind, tgs, cap, point)
     if key in _cache:
         return _cache[key]
-    spec, sp = spec_of(case), sim_params(case, tgs)
+    spec, sp = spec_of(case), sim_params(case, tgs, point=point)
     mnp = M.pack_model(spec)
     if cap is not None:
-        root, dof, act, _ = states(case, kind, tgs)
-        _cache[key] = root, dof, act, TreeHost(spec, root, dof, act).simulate(mnp, sim_params(case, tgs, cap))
+        root, dof, act, _ = states(case, kind, tgs, point=point)
+        _cache[key] = root, dof, act, TreeHost(spec, root, dof, act).simulate(mnp, sim_params(case, tgs, cap, point))
         return _cache[key]
+    shift = 1000 * SR.seed_shift(point, case.name()) if point is not None else 0
     if kind == "overflow":
-        root, dof, act = overflow_pool(spec, mnp, sp, POOL, case.overflow_seed or case.state_seed)
+        root, dof, act = overflow_pool(spec, mnp, sp, POOL, (case.overflow_seed or case.state_seed) + shift)
     else:
-        root, dof, act = dropped_pool(spec, mnp, sp, case.lanes, POOL, case.state_seed, sink=kind == "dropped")
+        root, dof, act = dropped_pool(spec, mnp, sp, case.lanes, POOL, case.state_seed + shift, sink=kind == "dropped")
     if kind == "settled":
         h = TreeHost(spec, root, dof, act)
         for _ in range(SETTLE_STEPS):
@@ -275,14 +285,14 @@ def states(case, kind, tgs=False, cap=None):
               PS.env_bad(moved.dof[..., 1], after.dof[..., 1], 0.25 * 2e-3, 0.25 * 2e-3) |
               PS.env_bad(moved.root[:, 0:7], after.root[:, 0:7], 0.25 * 2e-4, 0) |
               PS.env_bad(moved.root[:, 7:13], after.root[:, 7:13], 0.25 * 2e-3, 0.25 * 2e-3))
-    _cache["pool", case.name(), kind, tgs] = (n, int(fits.sum()))
+    _cache[("pool", case.name(), kind, tgs) + (() if point is None else (point,))] = (n, int(fits.sum()))
     flags = O.step_flips(mnp, sp, TreeHost(spec, root, dof, act), PS.STEP_DELTA, PS.STEP_DF)
     # overflow: at most half of the states may be ones where the cut does not matter to the oracle itself (its step
     # with room for every candidate stays within the tolerances of its step at capacity): past that, such a state is
     # passed over, so that a kernel that ignored the cut could not pass
     inert = np.zeros(n, bool)
     if kind == "overflow":
-        roomy = TreeHost(spec, root, dof, act).simulate(mnp, sim_params(case, tgs, ORACLE_MAXC))
+        roomy = TreeHost(spec, root, dof, act).simulate(mnp, sim_params(case, tgs, ORACLE_MAXC, point))
         inert[:] = True
         for _, a, b, atol, rtol in outside(roomy, after, n):
             inert &= ~PS.env_bad(a, b, atol, rtol)
@@ -366,14 +376,14 @@ def candidates_before(case, kind, tgs=False):
     return np.abs(num_candidates(M.pack_model(spec), sim_params(case, tgs), root, dof))
 
 
-def compare(test, case, kind, n, got, tgs=False, reach_cap=PS.REACH_CAP, cap=None):
+def compare(test, case, kind, n, got, tgs=False, reach_cap=PS.REACH_CAP, cap=None, point=None):
     """`got`: a TreeHost-like result (root, dof, sensors, dof_force, ncf) of one simulate of the case's first n states
     by the implementation under test.  Every env within the one-step tolerances of the fp64 oracle (positions 2e-4,
     velocities 2e-3 + 2e-3 |v|, DOF forces / sensors / net contact forces 1 % of the batch's largest), unless
     orc_step_flips puts its step at a discontinuity (parity_stats.assert_steps_explained: reach at most 5 %, no
     sensitivity fallback, nothing unexplained); finite; and the states moved.  Returns the exemption record."""
-    spec, sp = spec_of(case), sim_params(case, tgs, cap)
-    root, dof, act, ref = states(case, kind, tgs, cap)
+    spec, sp = spec_of(case), sim_params(case, tgs, cap, point)
+    root, dof, act, ref = states(case, kind, tgs, cap, point)
     for x in (got.root, got.dof, got.sensors, got.dof_force, got.ncf):
         assert np.isfinite(x).all()
     assert np.abs(got.dof[..., 0] - dof[:n, :, 0]).max() > 1e-3, "the step moved nothing"
