@@ -32,6 +32,19 @@
 #define MG_VGPR_ATTR
 #endif
 
+// head fetch (1): the static-grid k_env_step instances issue the wave's order entry and its actors' raw inputs
+// before / under the model tile's copy instead of after the block barrier (0: as the work-queue instances, in the item)
+#ifndef MG_HEAD_FETCH
+#define MG_HEAD_FETCH 1
+#endif
+// where the compact 16-lane k_env_step loads the task layer's per-env scalars (progress, potentials) and its action
+// lanes' column: 0 after the physics, where the task layer reads them; 1 at the start of the item; 2 after the last
+// substep, before outputs() (the PGS registers are dead there and outputs() / stage_state() hide the trip).  Every
+// other instance loads them at the start.
+#ifndef MG_TASK_PREFETCH_C16
+#define MG_TASK_PREFETCH_C16 2
+#endif
+
 namespace mgi {
 #ifdef MG_PHASE_TIMING
 // per-wave accumulators (one row of MG_NUM_PHASES per block; plain read-modify-writes by the block's own wave,
@@ -318,18 +331,57 @@ __device__ __forceinline__ void order_done(const MgOrder& ord, int grid_waves) {
   }
 }
 
+// The raw inputs of one lane's actor in k_env_step, fetched ahead of the model tile (MG_HEAD_FETCH): the actor, its
+// reset flag, its root row, and the lane's own DOF pair and action column.  None of it needs the tile: the lane's
+// DOF follows from the lane index and the model header alone, as in Team::init().
+struct EnvHead {
+  int a;
+  int64_t reset_in;
+  float root[13];
+  float qj, nu, act;
+#ifdef MG_PHASE_TIMING
+  unsigned long long t0;  // the wave's clock before the tile copy: load+pre then counts the copy and the barrier
+#endif
+};
+// the loads of EnvHead for actor `actor` (h.a, or n - 1 for a team past the batch, as in the item); the addresses are
+// those Team::load() and the clamp read in the item
+template <int T>
+__device__ __forceinline__ void env_head_fetch(EnvHead& h, int actor, const mg_model* __restrict__ m,
+                                               const mg_task_params& tp, const mg_state_views& v,
+                                               const mg_task_buffers& tb) {
+  const int tl = threadIdx.x % T, c0 = m->fixed_base ? 0 : 6, d = tl - c0;
+  const int na = tp.num_actions, nd = m->num_dofs;
+  const size_t ac = (size_t)actor;
+  h.reset_in = tb.reset[ac];
+  const float* root = v.root_states + 13 * ac;
+#pragma unroll
+  for (int k = 0; k < 13; k++) h.root[k] = root[k];
+  h.qj = h.nu = h.act = 0.0f;
+  if (d >= 0 && d + 1 < m->num_nodes) {  // Team::init(): node = d + 1 > 0
+    h.qj = v.dof_state[2 * nd * ac + 2 * d];
+    h.nu = v.dof_state[2 * nd * ac + 2 * d + 1];
+    if (tp.task_id == MG_TASK_CARTPOLE) {
+      if (d == 0) h.act = tb.actions[na * ac];
+    } else if (d < na) {
+      h.act = tb.actions[na * ac + d];
+    }
+  }
+}
+
 // one work item of k_env_step: the E1 teams of one wave (item = the wave's global index)
-template <int T, int MN, int MC, int MG, int MP, bool DR, bool RP, bool TGS = false, int LAY = 0>
+template <int T, int MN, int MC, int MG, int MP, bool DR, bool RP, bool TGS = false, int LAY = 0, bool HF = false>
 __device__ __forceinline__ void env_step_item(
     const mg_model* __restrict__ m, const mg::ModelTile<MN, MG, MP>& tile, mg::BankSlot<mg::TeamLDSOf<T, MN, MC, 0, MG, MP, LAY>, T>* lds,
     mg::DrTile<DR ? MN : 1, DR ? MG : 1>* drt, const mg_sim_params& p, const mg_task_params& tp, const mg_state_views& v,
-    const mg_task_buffers& tb, int n, const mg_replay& rp, int item, const MgOrder& ord) {
+    const mg_task_buffers& tb, int n, const mg_replay& rp, int item, const MgOrder& ord, const EnvHead* eh = nullptr) {
   using SH = Shape<T, MN, MC, MG, MP, 0, DR, LAY>;
   const int team = threadIdx.x / T;
   const int wt = (threadIdx.x & 63) / T;  // team index within the wave (ballot / shuffle positions)
   const int slot = item * SH::E1 + wt;
   const bool valid = slot < n;
-  const int a = ordered_actor(ord, slot, n, tp.num_agents);
+  int a;
+  if constexpr (HF) a = eh->a;
+  else a = ordered_actor(ord, slot, n, tp.num_agents);
   const int ac = valid ? a : n - 1;
   const int na = tp.num_actions, nd = m->num_dofs, ns = m->num_sensors;
   mg::TeamLDSOf<T, MN, MC, 0, MG, MP, LAY>& L = lds[team].v;
@@ -340,28 +392,49 @@ __device__ __forceinline__ void env_step_item(
     t.bind_dr(&drt[team]);
   }
   mg::wsync();
-  const int64_t reset_in = tb.reset[ac];
+  int64_t reset_in;
+  if constexpr (HF) reset_in = eh->reset_in;
+  else reset_in = tb.reset[ac];
   // the task layer's per-env scalars, loaded now so that their latency hides under the physics (nothing in the
   // step writes them before the task layer does); not for the compact 16-lane kernel, whose 168 registers it costs
-  // (profiles/r06/ab_task_prefetch.txt: Ant 65,536 -0.3 %, MA-Ant -0.4 %; Humanoid +0.6 %, Ant 8,192 +0.9 %)
-  constexpr bool kTaskPf = !(SH::TL::kCompact && T == 16);
+  // (profiles/r06/ab_task_prefetch.txt: Ant 65,536 -0.3 %, MA-Ant -0.4 %; Humanoid +0.6 %, Ant 8,192 +0.9 %): that
+  // one loads them, and its action lanes' column, after the last substep (MG_TASK_PREFETCH_C16)
+  constexpr int kTaskPf = !(SH::TL::kCompact && T == 16) ? 1 : (RP && MG_TASK_PREFETCH_C16 == 2 ? 0 : MG_TASK_PREFETCH_C16);
+  const bool alane = t.tl < na;  // self.actions: one lane per action column (na <= T, checked by mg_env_step)
   int64_t progress_in = 0;
-  float pot_in = 0.0f, prev_in = 0.0f;
-  if constexpr (kTaskPf) {
+  float pot_in = 0.0f, prev_in = 0.0f, act_in = 0.0f;
+  if constexpr (kTaskPf == 1) {
     progress_in = tb.progress[ac];
     pot_in = tb.potentials ? tb.potentials[ac] : 0.0f;
     prev_in = tb.potentials ? tb.prev_potentials[ac] : 0.0f;
   }
   t.ph_start();
+#ifdef MG_PHASE_TIMING
+  if (eh) t.tmark = eh->t0;
+#endif
   // pre_physics_step: clamp + effort (ant.py:281-285; humanoid.py:281-285; cartpole.py:159-163)
-  t.load(v.root_states + (size_t)13 * ac, v.dof_state + (size_t)2 * nd * ac, nullptr);
+  if constexpr (HF) {  // Team::load() on the rows fetched ahead
+    t.load_root(eh->root);
+    if (t.node > 0) {
+      t.qj = eh->qj;
+      t.nu = eh->nu;
+    }
+  } else {
+    t.load(v.root_states + (size_t)13 * ac, v.dof_state + (size_t)2 * nd * ac, nullptr);
+  }
   if (t.node > 0) {
     const int d = t.node - 1;
     float tau;
     if (tp.task_id == MG_TASK_CARTPOLE) {
-      tau = d == 0 ? mg::clampf(tb.actions[(size_t)na * ac], tp.clip_actions) * tp.power_scale : 0.0f;
+      float x = 0.0f;
+      if constexpr (HF) x = eh->act;
+      else if (d == 0) x = tb.actions[(size_t)na * ac];
+      tau = d == 0 ? mg::clampf(x, tp.clip_actions) * tp.power_scale : 0.0f;
     } else {
-      const float act = d < na ? mg::clampf(tb.actions[(size_t)na * ac + d], tp.clip_actions) : 0.0f;
+      float x = 0.0f;
+      if constexpr (HF) x = eh->act;
+      else if (d < na) x = tb.actions[(size_t)na * ac + d];
+      const float act = d < na ? mg::clampf(x, tp.clip_actions) : 0.0f;
       tau = act * tp.motor_effort[d] * tp.power_scale;
     }
     t.tau = tau;
@@ -378,6 +451,12 @@ __device__ __forceinline__ void env_step_item(
     // controlFrequencyInv: gym.simulate x cfi between one pre- and one post_physics_step (vec_task.py:381-384)
     const int nsub = p.substeps * (tp.control_freq_inv > 1 ? tp.control_freq_inv : 1);
     for (int st = 0; st < nsub; st++) t.substep();
+    if constexpr (kTaskPf == 2) {  // the task layer's inputs: the trip hides under outputs() and stage_state()
+      progress_in = tb.progress[ac];
+      pot_in = tb.potentials ? tb.potentials[ac] : 0.0f;
+      prev_in = tb.potentials ? tb.prev_potentials[ac] : 0.0f;
+      act_in = alane ? tb.actions[(size_t)na * ac + t.tl] : 0.0f;
+    }
     // no rigid-body states here: pose-only FK; DOF forces only where something reads them (the bound view, or the
     // Humanoid's observation: the reference's Ant and Cartpole never acquire a DOF-force tensor)
     t.template outputs<true>(L.st().sens,
@@ -402,12 +481,11 @@ __device__ __forceinline__ void env_step_item(
   float pot = 0.0f, prev = 0.0f, up[3] = {0, 0, 0}, hd[3] = {0, 0, 0};
   int64_t progress = (kTaskPf ? progress_in : tb.progress[ac]) + 1;
   int64_t reset = reset_in;
-  // self.actions: one lane per action column (na <= T, checked by mg_env_step)
-  const bool alane = t.tl < na;
-  const float act_l = alane ? mg::clampf(tb.actions[(size_t)na * ac + t.tl], tp.clip_actions) : 0.0f;
+  if constexpr (kTaskPf != 2) act_in = alane ? tb.actions[(size_t)na * ac + t.tl] : 0.0f;
+  const float act_l = alane ? mg::clampf(act_in, tp.clip_actions) : 0.0f;
   if (valid && alane && tb.actions_out) tb.actions_out[(size_t)na * a + t.tl] = act_l;
   if (tb.potentials) {
-    if constexpr (kTaskPf) { pot = pot_in; prev = prev_in; }
+    if constexpr (kTaskPf != 0) { pot = pot_in; prev = prev_in; }
     else { pot = tb.potentials[ac]; prev = tb.prev_potentials[ac]; }
   }
   if (do_reset) {  // reset_idx: one lane per DOF draws its noise; the leader resets root and potentials
@@ -554,12 +632,45 @@ __global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, 0, DR, LAY>::kThreads)) _
   __shared__ mg::DrTile<DR ? MN : 1, DR ? MG : 1> drt[DR ? E : 1];
   span_start(ord.clk, (int)blockIdx.x * W + (int)(threadIdx.x / 64));
   sort_totals_clear(ord);
-  mg::copy_tile(&tile, static_cast<const mg::ModelTile<MN, MG, MP>*>(timg));
+  using MT = mg::ModelTile<MN, MG, MP>;
+  constexpr int kTileRegs = mg::tile_pieces_per_lane<MT>(SH::kThreads);
+  if constexpr (SH::kStatic && MG_HEAD_FETCH && kTileRegs <= 16) {
+    // the static grid, one item per wave.  Head fetch: the wave's order entry is requested first; when it is back
+    // the actors' raw inputs and the tile's pieces go out together, and one wait covers them all before the tile
+    // is stored and the block meets at the barrier -- two trips to memory where there were four in a row (the
+    // tile piece by piece, the barrier, the order entry, the inputs).  A wave without an item (the last block's)
+    // fetches actor n - 1 as a team past the batch does, and writes nothing.
+    const int item = (int)blockIdx.x * W + (int)(threadIdx.x / 64);
+    EnvHead hd;
+#ifdef MG_PHASE_TIMING
+    hd.t0 = __builtin_amdgcn_s_memtime();
+#endif
+    const int slot = item * SH::E1 + (int)(threadIdx.x & 63) / T;
+    hd.a = ordered_actor(ord, slot, n, tp.num_agents);
+    uint4 tr[kTileRegs];
+    mg::copy_tile_issue<MT, SH::kThreads>(tr, static_cast<const MT*>(timg));
+    env_head_fetch<T>(hd, slot < n ? hd.a : n - 1, m, tp, v, tb);
+    mg::copy_tile_commit<MT, SH::kThreads>(&tile, tr);
+    __syncthreads();  // the only block-wide barrier: every later phase synchronises its own wave
+    if (item * SH::E1 < n)
+      env_step_item<T, MN, MC, MG, MP, DR, RP, TGS, LAY, true>(m, tile, lds, drt, p, tp, v, tb, n, rp, item, ord, &hd);
+    span_end(ord.clk, item);
+    order_done(ord, (int)gridDim.x * W);
+    return;
+  }
+#ifdef MG_PHASE_TIMING
+  EnvHead ht;  // the static grid's load+pre counts the tile copy and the barrier here too
+  ht.t0 = __builtin_amdgcn_s_memtime();
+  const EnvHead* const pht = SH::kStatic ? &ht : nullptr;
+#else
+  const EnvHead* const pht = nullptr;
+#endif
+  mg::copy_tile(&tile, static_cast<const MT*>(timg));
   __syncthreads();  // the only block-wide barrier: every later phase synchronises its own wave
   if constexpr (SH::kStatic) {
     // the static grid, one item per wave (one-wave blocks free their slot as soon as their wave is done)
     const int item = (int)blockIdx.x * W + (int)(threadIdx.x / 64);
-    if (item * SH::E1 < n) env_step_item<T, MN, MC, MG, MP, DR, RP, TGS, LAY>(m, tile, lds, drt, p, tp, v, tb, n, rp, item, ord);
+    if (item * SH::E1 < n) env_step_item<T, MN, MC, MG, MP, DR, RP, TGS, LAY>(m, tile, lds, drt, p, tp, v, tb, n, rp, item, ord, pht);
     span_end(ord.clk, item);
     order_done(ord, (int)gridDim.x * W);
   } else {

@@ -179,6 +179,33 @@ __device__ __forceinline__ void copy_tile(MT* t, const MT* img) {
   for (int i = threadIdx.x; i < (int)(sizeof(MT) / 16); i += blockDim.x) dst[i] = src[i];
 }
 
+// the same copy in two halves, for a kernel that has loads of its own to issue while the tile's are in flight: every
+// lane's pieces into registers (NT = the block's threads), then from the registers into the LDS tile.  Straight-line
+// code, so that the loads stay where they are issued: a lane past the last piece copies the last piece once more
+// (the same bytes to the same address as its owner).
+template <class MT>
+constexpr int tile_pieces_per_lane(int nt) { return (int)((sizeof(MT) / 16 + nt - 1) / nt); }
+template <class MT, int NT>
+__device__ __forceinline__ void copy_tile_issue(uint4 (&r)[tile_pieces_per_lane<MT>(NT)], const MT* img) {
+  const uint4* src = reinterpret_cast<const uint4*>(img);
+  constexpr int kLast = (int)(sizeof(MT) / 16) - 1;
+#pragma unroll
+  for (int k = 0; k < tile_pieces_per_lane<MT>(NT); k++) {
+    const int i = (int)threadIdx.x + k * NT;
+    r[k] = src[i < kLast ? i : kLast];
+  }
+}
+template <class MT, int NT>
+__device__ __forceinline__ void copy_tile_commit(MT* t, const uint4 (&r)[tile_pieces_per_lane<MT>(NT)]) {
+  uint4* dst = reinterpret_cast<uint4*>(t);
+  constexpr int kLast = (int)(sizeof(MT) / 16) - 1;
+#pragma unroll
+  for (int k = 0; k < tile_pieces_per_lane<MT>(NT); k++) {
+    const int i = (int)threadIdx.x + k * NT;
+    dst[i < kLast ? i : kLast] = r[k];
+  }
+}
+
 // Teams never span a wave, so the team phases synchronise their own wave only (rocPRIM's wave_barrier:
 // a wave's LDS operations complete in order; the wavefront-scope fences keep the compiler from moving
 // LDS accesses across the point).  No s_barrier: the other waves of the block run on independently.
@@ -3136,6 +3163,25 @@ struct Team {
   // ---------------------------------------------------------------- state I/O (gym layouts)
   __device__ __forceinline__ void load(const float* root, const float* dof, const float* act_tau, const float* orow = nullptr,
                        const float* tg = nullptr) {
+    load_root(root);
+    if (node > 0) {
+      qj = dof[2 * (node - 1)];
+      nu = dof[2 * (node - 1) + 1];
+      tau = act_tau ? act_tau[node - 1] : 0.0f;
+      tgt = tg ? tg[node - 1] : 0.0f;
+    }
+    if (OBJ && orow) {  // object row [p, q, v_com, w]: pose on every lane, twist on the object lanes
+      op = ld3(orow);
+      const float n = sqrtf(orow[3] * orow[3] + orow[4] * orow[4] + orow[5] * orow[5] + orow[6] * orow[6]);
+      for (int k = 0; k < 4; k++) oq[k] = orow[3 + k] / n;
+      if (objl) {
+        const int k = tl - ob0;
+        nu = k < 3 ? orow[10 + k] : orow[7 + k - 3];
+      }
+    }
+  }
+  // the root row of load(), from global memory or from registers (k_env_step's head fetch)
+  __device__ __forceinline__ void load_root(const float* root) {
     // root pose/twist: every lane reads the 13 floats (one cache line pair per actor) and normalises the
     // quaternion itself (the same operations on every lane: no shuffles from the leader)
     {
@@ -3157,21 +3203,6 @@ struct Team {
       V3 vo = ld3(root + 7) - cross(om, cw);
       float tw[6] = {om.x, om.y, om.z, vo.x, vo.y, vo.z};
       nu = tw[tl];
-    }
-    if (node > 0) {
-      qj = dof[2 * (node - 1)];
-      nu = dof[2 * (node - 1) + 1];
-      tau = act_tau ? act_tau[node - 1] : 0.0f;
-      tgt = tg ? tg[node - 1] : 0.0f;
-    }
-    if (OBJ && orow) {  // object row [p, q, v_com, w]: pose on every lane, twist on the object lanes
-      op = ld3(orow);
-      const float n = sqrtf(orow[3] * orow[3] + orow[4] * orow[4] + orow[5] * orow[5] + orow[6] * orow[6]);
-      for (int k = 0; k < 4; k++) oq[k] = orow[3 + k] / n;
-      if (objl) {
-        const int k = tl - ob0;
-        nu = k < 3 ? orow[10 + k] : orow[7 + k - 3];
-      }
     }
   }
 
