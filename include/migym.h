@@ -756,6 +756,97 @@ size_t mg_render_scratch_floats(const mg_sim* sim, int32_t n_sel, int32_t num_bo
  * misaligned scratch, a sim whose state is not bound. */
 int mg_render(mg_sim* sim, const mg_render_args* args, void* stream);
 
+/* ---- HumanoidAMP (humanoid_amp.py, amp/humanoid_amp_base.py, amp/utils_amp/motion_lib.py): the AMP humanoid as three
+ * launches per control step -- mg_amp_pre, mg_sim_simulate x controlFrequencyInv, mg_amp_post -- plus mg_amp_reset_idx
+ * (reset_idx(env_ids), all four StateInit modes, sampled from a device motion table) and mg_amp_obs_demo
+ * (fetch_amp_obs_demo).  All asynchronous on the caller's stream, no host synchronisation, no atomics.  One free-base
+ * 28-DOF, 15-body articulation per env; the sim must have rigid_body_states and net_contact_forces bound, and
+ * dof_targets (pd_control) or dof_actuation (effort mode).  New structs only; mg_task_buffers is reused. */
+#define MG_AMP_DOFS 28
+#define MG_AMP_BODIES 15
+#define MG_AMP_OBS 105          /* root_h 1 | root rot 6 | root vel 3 | root ang vel 3 | dof obs 52 | dof vel 28 | key 12 */
+#define MG_AMP_KEY_BODIES 4
+#define MG_AMP_FRAME_FLOATS 113 /* one motion frame, see mg_amp_views.motion_frames */
+#define MG_AMP_MAX_OBS_STEPS 16 /* numAMPObsSteps: 2 .. 16 */
+#define MG_AMP_NOISE_COLS 3     /* reset noise row [hybrid | motion | phase] */
+#define MG_AMP_INIT_DEFAULT 0
+#define MG_AMP_INIT_START 1
+#define MG_AMP_INIT_RANDOM 2
+#define MG_AMP_INIT_HYBRID 3
+typedef struct mg_amp_params {
+  /* _build_pd_action_offset_scale (humanoid_amp_base.py:262-295), computed in double on the host, rounded once */
+  float pd_action_offset[MG_AMP_DOFS], pd_action_scale[MG_AMP_DOFS];
+  float motor_effort[MG_AMP_DOFS];     /* actuator gears (effort mode: a * motor_effort * power_scale) */
+  float initial_dof_pos[MG_AMP_DOFS];  /* zero but right_shoulder_x = pi/2, left_shoulder_x = -pi/2 */
+  float initial_root[13];              /* z = 0.89, identity rotation, zero twist */
+  double dt;                           /* controlFrequencyInv * sim.dt, a Python double (humanoid_amp_base.py:75-76) */
+  float power_scale;
+  float termination_height;
+  float hybrid_init_prob;
+  float clip_actions, clip_obs;
+  int32_t max_episode_length;
+  int32_t enable_early_termination, local_root_obs, pd_control;
+  int32_t state_init;                  /* MG_AMP_INIT_* */
+  int32_t num_amp_obs_steps;
+  int32_t key_body[MG_AMP_KEY_BODIES]; /* right_hand, left_hand, right_foot, left_foot */
+  uint32_t contact_body_mask;          /* bit b: body b is one of env.contactBodies */
+  int32_t num_bodies;                  /* rigid-body rows per env (15) */
+} mg_amp_params;
+
+/* task-owned device tensors and the motion table (migym/motion.py) */
+typedef struct mg_amp_views {
+  float* dof_targets;        /* (N*28): the buffer the sim has bound as dof_targets (pd_control) */
+  float* dof_actuation;      /* (N*28): the buffer the sim has bound as dof_actuation (effort mode) */
+  float* amp_obs;            /* (N, num_amp_obs_steps, 105): slot 0 the current step, slot k the k-th before */
+  int64_t* terminate;        /* (N) _terminate_buf */
+  /* (F, 113) fp32, the frames of all motions back to back: root pos 3 | root rot 4 (xyzw) | root vel 3 | root ang
+   * vel 3 | local rotations 15 x 4 | dof vel 28 | key-body positions 4 x 3 */
+  const float* motion_frames;
+  const int32_t* motion_index;  /* (M, 2): first frame, frame count (>= 2) */
+  const double* motion_time;    /* (M, 3): frame dt, length = dt * (frames - 1), cumulative normalised weight */
+  int32_t num_motions;          /* M >= 1 */
+  int32_t num_frames;           /* F */
+} mg_amp_views;
+size_t mg_amp_params_sizeof(void);
+size_t mg_amp_views_sizeof(void);
+
+/* pre_physics_step (humanoid_amp_base.py:362-374, 419-421), one launch: actions_out = clamp(actions, +-clip_actions);
+ * pd_control: dof_targets = pd_action_offset + pd_action_scale * actions_out (a product, then a sum: no FMA); else
+ * dof_actuation = actions_out * motor_effort * power_scale. */
+int mg_amp_pre(mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* views, const mg_task_buffers* tb,
+               void* stream);
+
+/* post_physics_step of both classes + the VecTask.step tail (humanoid_amp_base.py:376-390, 494-562,
+ * humanoid_amp.py:87-96, 274-333), one launch, per env: progress += 1; the 105 observations of
+ * compute_humanoid_observations from root_states, dof_state and the key bodies' rigid_body_states rows; reward 1;
+ * compute_humanoid_reset (fallen = any signed net-contact-force component > 0.1 on a non-contact body AND any
+ * non-contact body below termination_height AND progress > 1; reset = progress >= max_episode_length - 1 or
+ * terminated), reset and terminate written separately; the AMP history shifted by one slot, slot 0 =
+ * build_amp_observations; timeout, obs clamp, out_pack.  It resets nothing (the reference's step does not).
+ * state: NULL = the sim's bound views; else its root_states, dof_state, rigid_body_states and net_contact_forces are
+ * taken as the post-simulate state (physics-free replay). */
+int mg_amp_post(mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* views, const mg_task_buffers* tb,
+                const mg_state_views* state, void* stream);
+
+/* reset_idx(env_ids) (humanoid_amp.py:146-256), one launch, one 32-lane team per listed id.  tb->noise: (n, 3) U(0,1)
+ * rows BY LIST POSITION, [hybrid | motion | phase]; NULL = the counter RNG keyed by (seed, env_offset + env,
+ * step_counter | 2^62, column).  Hybrid takes the reference path when u < hybrid_init_prob; motion id = the first
+ * index whose cumulative weight exceeds u; time = u * length (Start: 0).  Reference path: root row and DOF state from
+ * the motion (MotionLib.get_motion_state: frame index, blend and times in fp64, lerp / slerp / exp maps in fp32,
+ * velocities of frame idx0 unblended), the AMP history from the motion at t - k dt.  Default path: initial_root and
+ * initial_dof_pos, the history copies of the current slot.  Both: progress = reset = terminate = 0, the env's
+ * observation row and AMP slot 0 from the written root / DOF state and the rigid_body_states rows AS BOUND (not
+ * refreshed: the reference reads its stale _rigid_body_pos here too).  A repeated id writes the same values twice
+ * when its noise rows agree; an id outside 0..N-1 is skipped. */
+int mg_amp_reset_idx(mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* views, const mg_task_buffers* tb,
+                     const int32_t* ids, int32_t n, void* stream);
+
+/* fetch_amp_obs_demo(num_samples) (humanoid_amp.py:108-133): out (num_samples, num_amp_obs_steps, 105) from the
+ * motion table alone; sample i draws [motion | phase] from noise (num_samples, 2), or NULL = the counter RNG keyed by
+ * (seed, i, counter | 2^61, column); slot k is build_amp_observations of the motion at t - k dt.  Needs no sim. */
+int mg_amp_obs_demo(const mg_amp_params* ap, const mg_amp_views* views, const float* noise, uint64_t seed,
+                    uint64_t counter, float* out, int32_t num_samples, void* stream);
+
 /* Measurement aid (no reference counterpart; bench.py's roofline.kernel_ms): the device-side duration of the
  * fused step kernel, from the first wave's start to the last wave's end on the GPU's constant wall clock
  * (wall_clock64, hipDeviceAttributeWallClockRate), so that no launch, queue or event-packet overhead is in it.

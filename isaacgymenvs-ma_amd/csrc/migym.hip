@@ -12,6 +12,7 @@
 #include "dynamics_tensors.hpp"
 #include "render.hpp"
 #include "anymal_task.hpp"  // as reach_task.hpp: restores FMA contraction at its end
+#include "amp_task.hpp"     // likewise
 #include "reach_task.hpp"   // before hand_task.hpp: that header leaves FMA contraction off for the rest of this file
 #include "hand_task.hpp"
 #include "task.hpp"
@@ -1532,6 +1533,103 @@ int mg_render(mg_sim* sim, const mg_render_args* a, void* stream) {
   hipLaunchKernelGGL(mgrd::k_render_trace, dim3((unsigned)(tiles * a->n_sel)), dim3(mgrd::kTile),
                      sizeof(float) * mgrd::kRec * (size_t)P + 3 * mgrd::kTile, (hipStream_t)stream, t);
   return check_launch("mg_render (trace)");
+}
+
+// ---- HumanoidAMP: the task layer around mg_sim_simulate (amp_task.hpp)
+size_t mg_amp_params_sizeof(void) { return sizeof(mg_amp_params); }
+size_t mg_amp_views_sizeof(void) { return sizeof(mg_amp_views); }
+
+// the constants every AMP entry point relies on for its indexing
+static int amp_params_ok(const mg_amp_params* ap, const mg_amp_views* v, const char* who) {
+  if (!ap || !v) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
+  if (ap->num_bodies != MG_AMP_BODIES) return fail(MG_EINVAL, std::string(who) + ": num_bodies must be 15");
+  for (int k = 0; k < MG_AMP_KEY_BODIES; k++)
+    if (ap->key_body[k] < 0 || ap->key_body[k] >= MG_AMP_BODIES)
+      return fail(MG_EINVAL, std::string(who) + ": key_body out of range");
+  if (ap->num_amp_obs_steps < 2 || ap->num_amp_obs_steps > MG_AMP_MAX_OBS_STEPS)
+    return fail(MG_EINVAL, std::string(who) + ": num_amp_obs_steps must be 2 .. 16");
+  if (ap->state_init < MG_AMP_INIT_DEFAULT || ap->state_init > MG_AMP_INIT_HYBRID)
+    return fail(MG_EINVAL, std::string(who) + ": unknown state_init");
+  return MG_OK;
+}
+
+static int amp_motions_ok(const mg_amp_views* v, const char* who) {
+  if (!v->motion_frames || !v->motion_index || !v->motion_time || v->num_motions < 1 || v->num_frames < 2)
+    return fail(MG_EINVAL, std::string(who) + ": needs a motion table (motion_frames, motion_index, motion_time)");
+  return MG_OK;
+}
+
+// a bound free-base 28-DOF, 15-body sim
+static int amp_args_ok(const mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* v, const mg_task_buffers* tb,
+                       const char* who) {
+  if (!sim || !tb) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
+  if (int rc = amp_params_ok(ap, v, who)) return rc;
+  if (!sim->bound) return fail(MG_EINVAL, std::string(who) + ": sim not bound");
+  const mg_model& m = sim->host_model;
+  if (m.fixed_base || m.obj_type || m.num_nodes - 1 != MG_AMP_DOFS || m.num_bodies != MG_AMP_BODIES)
+    return fail(MG_EINVAL, std::string(who) + ": needs a free-base model of 28 DOFs and 15 bodies without a free object");
+  return MG_OK;
+}
+
+int mg_amp_pre(mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* views, const mg_task_buffers* tb,
+               void* stream) {
+  if (int rc = amp_args_ok(sim, ap, views, tb, "mg_amp_pre")) return rc;
+  if (!tb->actions) return fail(MG_EINVAL, "mg_amp_pre: needs actions");
+  float* out = ap->pd_control ? views->dof_targets : views->dof_actuation;
+  const float* bound = ap->pd_control ? sim->views.dof_targets : sim->views.dof_actuation;
+  if (!out || out != bound)
+    return fail(MG_EINVAL, ap->pd_control
+                               ? "mg_amp_pre: views.dof_targets is not the buffer the sim has bound as dof_targets"
+                               : "mg_amp_pre: views.dof_actuation is not the buffer the sim has bound as dof_actuation");
+  if (sim->n == 0) return MG_OK;
+  const long long total = (long long)sim->n * MG_AMP_DOFS;
+  hipLaunchKernelGGL(mgh::k_amp_pre, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *ap,
+                     tb->actions, tb->actions_out, out, total);
+  return check_launch("mg_amp_pre");
+}
+
+int mg_amp_post(mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* views, const mg_task_buffers* tb,
+                const mg_state_views* state, void* stream) {
+  if (int rc = amp_args_ok(sim, ap, views, tb, "mg_amp_post")) return rc;
+  if (!tb->obs || !tb->rew || !tb->reset || !tb->progress || !tb->timeout || !views->amp_obs || !views->terminate)
+    return fail(MG_EINVAL, "mg_amp_post: needs obs, rew, reset, progress, timeout, amp_obs and terminate");
+  const mg_state_views& s = state ? *state : sim->views;
+  if (!s.root_states || !s.dof_state || !s.rigid_body_states || !s.net_contact_forces)
+    return fail(MG_EINVAL, "mg_amp_post: needs root_states, dof_state, rigid_body_states and net_contact_forces");
+  if (sim->n == 0) return MG_OK;
+  mgh::AmpState st{s.root_states, s.dof_state, s.rigid_body_states, s.net_contact_forces};
+  hipLaunchKernelGGL(mgh::k_amp_post, dim3((sim->n + mgh::kEnvs - 1) / mgh::kEnvs), dim3(64), 0, (hipStream_t)stream,
+                     *ap, *views, *tb, st, sim->n);
+  return check_launch("mg_amp_post");
+}
+
+int mg_amp_reset_idx(mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* views, const mg_task_buffers* tb,
+                     const int32_t* ids, int32_t n, void* stream) {
+  if (int rc = amp_args_ok(sim, ap, views, tb, "mg_amp_reset_idx")) return rc;
+  if (n < 0 || (n > 0 && !ids) || !tb->obs || !tb->reset || !tb->progress || !views->amp_obs || !views->terminate ||
+      !sim->views.root_states || !sim->views.dof_state || !sim->views.rigid_body_states)
+    return fail(MG_EINVAL, "mg_amp_reset_idx: bad arguments");
+  if (ap->state_init != MG_AMP_INIT_DEFAULT)
+    if (int rc = amp_motions_ok(views, "mg_amp_reset_idx")) return rc;
+  if (n == 0 || sim->n == 0) return MG_OK;
+  mg_task_buffers t = *tb;
+  t.step_counter = tb->step_counter | (1ull << 62);   // the manual-reset stream of the counter RNG, as mg_reset_idx
+  mgh::AmpState st{sim->views.root_states, sim->views.dof_state, sim->views.rigid_body_states,
+                   sim->views.net_contact_forces};
+  hipLaunchKernelGGL(mgh::k_amp_reset_idx, dim3((n + mgh::kEnvs - 1) / mgh::kEnvs), dim3(64), 0, (hipStream_t)stream,
+                     *ap, *views, t, st, ids, n, sim->n);
+  return check_launch("mg_amp_reset_idx");
+}
+
+int mg_amp_obs_demo(const mg_amp_params* ap, const mg_amp_views* views, const float* noise, uint64_t seed,
+                    uint64_t counter, float* out, int32_t num_samples, void* stream) {
+  if (int rc = amp_params_ok(ap, views, "mg_amp_obs_demo")) return rc;
+  if (int rc = amp_motions_ok(views, "mg_amp_obs_demo")) return rc;
+  if (num_samples < 0 || (num_samples > 0 && !out)) return fail(MG_EINVAL, "mg_amp_obs_demo: bad arguments");
+  if (num_samples == 0) return MG_OK;
+  hipLaunchKernelGGL(mgh::k_amp_obs_demo, dim3((num_samples + mgh::kEnvs - 1) / mgh::kEnvs), dim3(64), 0,
+                     (hipStream_t)stream, *ap, *views, noise, seed, counter | (1ull << 61), out, num_samples);
+  return check_launch("mg_amp_obs_demo");
 }
 
 }  // extern "C"

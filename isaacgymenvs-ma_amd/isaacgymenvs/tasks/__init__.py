@@ -1,1 +1,2 @@
-from migym.tasks import isaacgym_task_map, Ant, Humanoid, Cartpole, FrankaReachMA, Anymal  # noqa: F401
+from migym.tasks import isaacgym_task_map, Ant, Humanoid, Cartpole, FrankaReachMA, Anymal, \
+    HumanoidAMP  # noqa: F401

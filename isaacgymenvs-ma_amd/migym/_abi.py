@@ -179,6 +179,30 @@ class AnymalViews(C.Structure):
     _fields_ = [("commands", C.c_void_p), ("dof_targets", C.c_void_p)]
 
 
+MG_AMP_DOFS, MG_AMP_BODIES, MG_AMP_OBS, MG_AMP_KEY_BODIES = 28, 15, 105, 4
+MG_AMP_FRAME_FLOATS, MG_AMP_MAX_OBS_STEPS, MG_AMP_NOISE_COLS = 113, 16, 3
+MG_AMP_INIT = {"Default": 0, "Start": 1, "Random": 2, "Hybrid": 3}   # HumanoidAMP.StateInit
+
+
+class AmpParams(C.Structure):
+    """mg_amp_params: the constants of HumanoidAMP (taskdefs.amp_params)."""
+    _fields_ = [("pd_action_offset", C.c_float * MG_AMP_DOFS), ("pd_action_scale", C.c_float * MG_AMP_DOFS),
+                ("motor_effort", C.c_float * MG_AMP_DOFS), ("initial_dof_pos", C.c_float * MG_AMP_DOFS),
+                ("initial_root", C.c_float * 13), ("dt", C.c_double), ("power_scale", C.c_float),
+                ("termination_height", C.c_float), ("hybrid_init_prob", C.c_float), ("clip_actions", C.c_float),
+                ("clip_obs", C.c_float), ("max_episode_length", C.c_int32), ("enable_early_termination", C.c_int32),
+                ("local_root_obs", C.c_int32), ("pd_control", C.c_int32), ("state_init", C.c_int32),
+                ("num_amp_obs_steps", C.c_int32), ("key_body", C.c_int32 * MG_AMP_KEY_BODIES),
+                ("contact_body_mask", C.c_uint32), ("num_bodies", C.c_int32)]
+
+
+class AmpViews(C.Structure):
+    """mg_amp_views: the task-owned device tensors of HumanoidAMP and its motion table (migym/motion.py)."""
+    _fields_ = [("dof_targets", C.c_void_p), ("dof_actuation", C.c_void_p), ("amp_obs", C.c_void_p),
+                ("terminate", C.c_void_p), ("motion_frames", C.c_void_p), ("motion_index", C.c_void_p),
+                ("motion_time", C.c_void_p), ("num_motions", C.c_int32), ("num_frames", C.c_int32)]
+
+
 class RenderArgs(C.Structure):
     """mg_render_args: one ray-cast of the selected envs' collision geometry (migym/render.py)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fov_y", C.c_float), ("eye_offset", C.c_float * 3),
@@ -265,6 +289,16 @@ EXPORTS = {
                                  C.POINTER(StateViews), C.c_void_p]),
     "mg_anymal_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(AnymalParams), C.POINTER(AnymalViews),
                                       C.POINTER(TaskBuffers), C.c_void_p, C.c_int32, C.c_void_p]),
+    "mg_amp_params_sizeof": (C.c_size_t, []),
+    "mg_amp_views_sizeof": (C.c_size_t, []),
+    "mg_amp_pre": (C.c_int, [C.c_void_p, C.POINTER(AmpParams), C.POINTER(AmpViews), C.POINTER(TaskBuffers),
+                             C.c_void_p]),
+    "mg_amp_post": (C.c_int, [C.c_void_p, C.POINTER(AmpParams), C.POINTER(AmpViews), C.POINTER(TaskBuffers),
+                              C.POINTER(StateViews), C.c_void_p]),
+    "mg_amp_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(AmpParams), C.POINTER(AmpViews), C.POINTER(TaskBuffers),
+                                   C.c_void_p, C.c_int32, C.c_void_p]),
+    "mg_amp_obs_demo": (C.c_int, [C.POINTER(AmpParams), C.POINTER(AmpViews), C.c_void_p, C.c_uint64, C.c_uint64,
+                                  C.c_void_p, C.c_int32, C.c_void_p]),
     "mg_render_args_sizeof": (C.c_size_t, []),
     "mg_render_scratch_floats": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
     "mg_render": (C.c_int, [C.c_void_p, C.POINTER(RenderArgs), C.c_void_p]),
@@ -292,7 +326,8 @@ def check_layout(lib):
              "mg_dr_apply_args_sizeof": C.sizeof(DrApplyArgs), "mg_dr_noise_args_sizeof": C.sizeof(DrNoiseArgs),
              "mg_osc_args_sizeof": C.sizeof(OscArgs), "mg_reach_params_sizeof": C.sizeof(ReachParams),
              "mg_reach_views_sizeof": C.sizeof(ReachViews), "mg_anymal_params_sizeof": C.sizeof(AnymalParams),
-             "mg_anymal_views_sizeof": C.sizeof(AnymalViews), "mg_render_args_sizeof": C.sizeof(RenderArgs)}
+             "mg_anymal_views_sizeof": C.sizeof(AnymalViews), "mg_render_args_sizeof": C.sizeof(RenderArgs),
+             "mg_amp_params_sizeof": C.sizeof(AmpParams), "mg_amp_views_sizeof": C.sizeof(AmpViews)}
     for fn, py in sizes.items():
         c = getattr(lib, fn)()
         if c != py:

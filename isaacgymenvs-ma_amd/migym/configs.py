@@ -280,6 +280,27 @@ TASKS["Anymal"] = {
 }
 
 
+# HumanoidAMP (cfg/task/HumanoidAMP.yaml): only the keys the task reads.  Neither the AMP humanoid nor a motion clip is
+# shipped: env.asset.modelTable names a JSON model table (tools/build_models.py amp_humanoid writes one), or assetRoot +
+# assetFileName the MJCF; env.motion_file names a clip (.npy / .npz / .yaml), absolute or under env.asset.motionRoot.
+TASKS["HumanoidAMP"] = {
+    "name": "HumanoidAMP",
+    "env": {
+        "numEnvs": 4096, "envSpacing": 5, "episodeLength": 300, "cameraFollow": True, "enableDebugVis": False,
+        "pdControl": True, "powerScale": 1.0, "controlFrequencyInv": 2, "stateInit": "Random", "hybridInitProb": 0.5,
+        "numAMPObsSteps": 2, "localRootObs": False, "contactBodies": ["right_foot", "left_foot"],
+        "terminationHeight": 0.5, "enableEarlyTermination": True,
+        "motion_file": "amp_humanoid_run.npy",
+        "asset": {"assetRoot": "../../assets", "assetFileName": "mjcf/amp_humanoid.xml",
+                  "motionRoot": "../../assets/amp/motions"},
+        "plane": dict(_LOCO_PLANE),
+    },
+    "sim": _sim(dt=0.0166, num_position_iterations=4, num_velocity_iterations=0, contact_offset=0.02, rest_offset=0.0,
+                bounce_threshold_velocity=0.2, max_depenetration_velocity=10.0, contact_collection=2),
+    "task": {"randomize": False},
+}
+
+
 def resolve_default(default, arg):
     """``${resolve_default:d,x}`` (isaacgymenvs/__init__.py:11)."""
     return default if arg in ("", None) else arg

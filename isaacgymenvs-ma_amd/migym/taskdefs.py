@@ -400,3 +400,98 @@ def anymal_params(cfg: dict, spec: M.ModelSpec) -> _abi.AnymalParams:
     ap.clip_obs = float(env.get("clipObservations", math.inf))
     ap.max_episode_length = int(float(learn["episodeLength_s"]) / dt + 0.5)   # anymal.py:95
     return ap
+
+
+# ---- HumanoidAMP (humanoid_amp.py, amp/humanoid_amp_base.py)
+AMP_KEY_BODY_NAMES = ["right_hand", "left_hand", "right_foot", "left_foot"]   # humanoid_amp_base.py:47
+AMP_DOF_OFFSETS = [0, 3, 6, 9, 10, 13, 14, 17, 18, 21, 24, 25, 28]            # humanoid_amp_base.py:42
+# no fused-kernel task id and no shipped table; z = the start pose (humanoid_amp_base.py:209); 48 contacts and the
+# model's 34 lanes put it on the (64, 40, 48, 48, 192) instance
+TASK_INFO["HumanoidAMP"] = (None, None, _abi.MG_AMP_OBS, _abi.MG_AMP_DOFS, 0.89, 48)
+RENDER_DEFAULTS["HumanoidAMP"] = dict(width=320, height=240, fov_deg=60.0, eye=(0.0, -3.0, 0.1),
+                                      target=(0.0, 0.0, 0.1), follow=True)   # _init_camera: 3 m along -y
+
+
+def amp_spec(spec: M.ModelSpec, cfg: dict) -> M.ModelSpec:
+    """The AMP humanoid as the task configures it, on a copy (humanoid_amp_base.py:183-187, 237-240).  pdControl:
+    every DOF is a position drive whose gains are the MJCF joint's stiffness and damping, which is how gym's DOF
+    properties read them (DOF_MODE_POS), and no passive spring remains.  Otherwise DOF_MODE_NONE: efforts only, the
+    joint springs passive, as for Humanoid."""
+    import copy
+    spec = copy.deepcopy(spec)
+    if spec.num_dofs != _abi.MG_AMP_DOFS or len(spec.bodies) != _abi.MG_AMP_BODIES or spec.fixed_base:
+        raise ValueError("HumanoidAMP needs the free-base AMP humanoid: 28 DOFs, 15 bodies")
+    if bool(cfg["env"]["pdControl"]):
+        for n in spec.nodes[1:]:
+            n.drive_kp, n.stiffness = float(n.stiffness), 0.0
+    spec.angular_damping = 0.01          # asset_options.angular_damping
+    spec.max_angular_velocity = 100.0    # asset_options.max_angular_velocity
+    return spec
+
+
+def amp_action_offset_scale(spec: M.ModelSpec):
+    """_build_pd_action_offset_scale (humanoid_amp_base.py:262-295): 3-DOF joints get +-pi, 1-DOF joints their middle
+    +- 0.7 of their range.  The limits are gym's fp32 values; from them on the arithmetic is numpy double, rounded to
+    fp32 once at the end (the reference's own intermediate precision depends on the numpy version's scalar promotion;
+    the two agree to an fp32 ulp)."""
+    import numpy as np
+    lo, hi = dof_limits(spec)
+    lim_low = np.array(lo, np.float32).astype(np.float64)
+    lim_high = np.array(hi, np.float32).astype(np.float64)
+    for j in range(len(AMP_DOF_OFFSETS) - 1):
+        o, size = AMP_DOF_OFFSETS[j], AMP_DOF_OFFSETS[j + 1] - AMP_DOF_OFFSETS[j]
+        if size == 3:
+            lim_low[o:o + 3] = -np.pi
+            lim_high[o:o + 3] = np.pi
+        else:
+            curr_low, curr_high = lim_low[o], lim_high[o]
+            curr_mid = 0.5 * (curr_high + curr_low)
+            curr_scale = 0.7 * (curr_high - curr_low)
+            lim_low[o] = curr_mid - curr_scale
+            lim_high[o] = curr_mid + curr_scale
+    offset = 0.5 * (lim_high + lim_low)
+    scale = 0.5 * (lim_high - lim_low)
+    return np.asarray(offset, np.float32), np.asarray(scale, np.float32)
+
+
+def amp_params(cfg: dict, spec: M.ModelSpec) -> _abi.AmpParams:
+    """HumanoidAMP constants (humanoid_amp_base.py:54-76, 105-109, 189-258; humanoid_amp.py:60-64)."""
+    env = cfg["env"]
+    ap = _abi.AmpParams()
+    offset, scale = amp_action_offset_scale(spec)
+    gears = {a["joint"]: float(a["gear"]) for a in spec.actuators}
+    for j, name in enumerate(spec.dof_names):
+        ap.pd_action_offset[j], ap.pd_action_scale[j] = float(offset[j]), float(scale[j])
+        ap.motor_effort[j] = gears.get(name, 0.0)
+        ap.initial_dof_pos[j] = 0.0
+    ap.initial_dof_pos[spec.dof_names.index("right_shoulder_x")] = 0.5 * math.pi
+    ap.initial_dof_pos[spec.dof_names.index("left_shoulder_x")] = -0.5 * math.pi
+    root = [0.0, 0.0, 0.89, 0.0, 0.0, 0.0, 1.0] + [0.0] * 6
+    for c, x in enumerate(root):
+        ap.initial_root[c] = x
+    ap.dt = max(1, int(env.get("controlFrequencyInv", 1))) * float(cfg["sim"]["dt"])   # a Python double, not a C float
+    ap.power_scale = float(env["powerScale"])
+    ap.termination_height = float(env["terminationHeight"])
+    ap.hybrid_init_prob = float(env["hybridInitProb"])
+    ap.clip_actions = float(env.get("clipActions", math.inf))
+    ap.clip_obs = float(env.get("clipObservations", math.inf))
+    ap.max_episode_length = int(env["episodeLength"])
+    ap.enable_early_termination = int(bool(env["enableEarlyTermination"]))
+    ap.local_root_obs = int(bool(env["localRootObs"]))
+    ap.pd_control = int(bool(env["pdControl"]))
+    if env["stateInit"] not in _abi.MG_AMP_INIT:
+        raise ValueError(f"stateInit must be one of {sorted(_abi.MG_AMP_INIT)}, got {env['stateInit']!r}")
+    ap.state_init = _abi.MG_AMP_INIT[env["stateInit"]]
+    steps = int(env["numAMPObsSteps"])
+    if not 2 <= steps <= _abi.MG_AMP_MAX_OBS_STEPS:
+        raise ValueError(f"numAMPObsSteps must be 2 .. {_abi.MG_AMP_MAX_OBS_STEPS}, got {steps}")
+    ap.num_amp_obs_steps = steps
+    names = [b.name for b in spec.bodies]
+    for k, name in enumerate(AMP_KEY_BODY_NAMES):
+        ap.key_body[k] = names.index(name)
+    mask = 0
+    for name in env["contactBodies"]:
+        mask |= 1 << names.index(name)
+    ap.contact_body_mask = mask
+    ap.num_bodies = len(names)
+    return ap

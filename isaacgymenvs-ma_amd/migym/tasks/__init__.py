@@ -4,6 +4,7 @@ from .cartpole import Cartpole
 from .shadow_hand import ShadowHand
 from .franka_reach_ma import FrankaReachMA
 from .anymal import Anymal
+from .humanoid_amp import HumanoidAMP
 
 isaacgym_task_map = {
     "Ant": Ant,
@@ -13,4 +14,5 @@ isaacgym_task_map = {
     "ShadowHand": ShadowHand,
     "FrankaReachMA": FrankaReachMA,
     "Anymal": Anymal,
+    "HumanoidAMP": HumanoidAMP,
 }

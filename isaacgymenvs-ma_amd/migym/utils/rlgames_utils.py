@@ -95,6 +95,8 @@ class RLGPUEnv:
     def get_env_info(self):
         info = {"action_space": self.env.action_space, "observation_space": self.env.observation_space,
                 "agents": self.env.num_agents}
+        if hasattr(self.env, "amp_observation_space"):   # rlgames_utils.py:265-266 (HumanoidAMP)
+            info["amp_observation_space"] = self.env.amp_observation_space
         if self.env.num_states > 0:
             info["state_space"] = self.env.state_space
         return info

@@ -34,6 +34,10 @@ them from migym/assets/*.json.
             tests/golden/anymal_c.json and not shipped under migym/assets: 13 bodies (base, then
             {LF,RF,LH,RH}_{HIP,THIGH,SHANK}), 12 DOFs, 37 primitive geoms, the URDF's inertials (52.13 kg) and its
             effort limits (80 N m); the task sets the drive gains (env.control).
+  HumanoidAMP  assets/mjcf/amp_humanoid.xml (amp/humanoid_amp_base.py:176-226: angular_damping 0.01,
+            max_angular_velocity 100, self-collision filter 0).  A TEST FIXTURE, written to
+            tests/golden/amp_humanoid.json and not shipped under migym/assets: 15 bodies, 28 DOFs, 18 geoms, 122 self
+            pairs, 48.89 kg; the joints keep the MJCF's stiffness / damping (the task turns them into drive gains).
 """
 import json
 import os
@@ -183,6 +187,19 @@ def anymal_c():
     return spec
 
 
+AMP_MJCF = "assets/mjcf/amp_humanoid.xml"
+AMP_JSON = os.path.join(HERE, "..", "tests", "golden", "amp_humanoid.json")
+
+
+def amp_humanoid():
+    """The AMP humanoid as the reference's HumanoidAMP loads it (humanoid_amp_base.py:183-187, 224-226)."""
+    spec = M.load_mjcf(os.path.join(REF, AMP_MJCF), "amp_humanoid", self_collision=True)
+    spec.sensors = [spec.body_index("right_foot"), spec.body_index("left_foot")]   # humanoid_amp_base.py:193-198
+    spec.angular_damping = 0.01
+    spec.max_angular_velocity = 100.0
+    return spec
+
+
 HAND_FINGERTIPS = ["robot0:ffdistal", "robot0:mfdistal", "robot0:rfdistal", "robot0:lfdistal", "robot0:thdistal"]
 HAND_TENDONS = ["robot0:T_FFJ1c", "robot0:T_MFJ1c", "robot0:T_RFJ1c", "robot0:T_LFJ1c"]
 
@@ -256,7 +273,9 @@ def main():
     fr.to_json(FRANKA_JSON)
     an = anymal_c()
     an.to_json(ANYMAL_JSON)
-    for s in (ant, hum, cp, sh, fr, an):
+    amp = amp_humanoid()
+    amp.to_json(AMP_JSON)
+    for s in (ant, hum, cp, sh, fr, an, amp):
         print(f"{s.name}: nodes={len(s.nodes)} dofs={s.num_dofs} bodies={len(s.bodies)} geoms={len(s.geoms)} "
               f"pairs={len(s.pairs)} mass={s.total_mass():.4f} sensors={s.sensors}")
 
@@ -272,6 +291,11 @@ if __name__ == "__main__":
         # the Anymal table alone (Anymal's env.asset.modelTable): `build_models.py anymal_c [OUT.json]`
         path = sys.argv[2] if len(sys.argv) > 2 else ANYMAL_JSON
         anymal_c().to_json(path)
+        print("wrote", path)
+    elif sys.argv[1:2] == ["amp_humanoid"]:
+        # the AMP humanoid's table alone (HumanoidAMP's env.asset.modelTable): `build_models.py amp_humanoid [OUT.json]`
+        path = sys.argv[2] if len(sys.argv) > 2 else AMP_JSON
+        amp_humanoid().to_json(path)
         print("wrote", path)
     else:
         main()
