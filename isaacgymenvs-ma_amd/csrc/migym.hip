@@ -611,17 +611,19 @@ int mg_sim_create(const mg_model* model, const mg_sim_params* params, int32_t nu
   s->d_span = nullptr;
   s->span_cap = s->span_next = s->span_stride = 0;
   // default (same box, M env-steps/s unordered -> ordered): the sort for ShadowHand and Humanoid from
-  // 16,384 envs and for Ant from 32,768 one-agent envs (ShadowHand 16,384 18.9 -> 20.1, in-kernel lists 20.0;
-  // Humanoid 32,768 33.9 -> 37.3, lists 37.0; Ant 65,536 152.7 -> 157.8, lists 119.4: their hot-bucket atomics);
-  // off for MA-Ant (8,192 -0.8 %, 65,536 -1.0 % sorted), Cartpole and the smaller batches (Ant 16,384 within
-  // noise, ShadowHand 4,096 -2 %: the sort's two launches outweigh the tail they save).
+  // 16,384 envs and for Ant from 16,384 one-agent envs (ShadowHand 16,384 18.9 -> 20.1, in-kernel lists 20.0;
+  // Humanoid 32,768 33.9 -> 37.3, lists 37.0; Ant 65,536 152.7 -> 157.8, lists 119.4: their hot-bucket atomics;
+  // Ant 16,384: within noise under the last substep's row count as the key, 138.0 -> 148.4 under round 8's key counted
+  // from the state the step leaves behind, profiles/r08/ab_zero_rows.txt);
+  // off for MA-Ant (8,192 -0.8 %, 65,536 -1.0 % sorted; 8,192 +0.8 % under the round-8 key, inside three spreads),
+  // Cartpole and the smaller batches (ShadowHand 4,096 -2 %: the sort's two launches outweigh the tail they save).
   // MIGYM_ORDER = off | lists | sort | sort:K (sort every K-th launch only; A/B: the order goes stale within two
   // steps) overrides.
   {
     const int T = mgi::team_size(s->host_model, s->params.max_contacts);
     const int A = params->agents > 1 ? params->agents : 1;
     if (T >= 32) s->order_mode = num_envs >= 16384 ? kOrderSort : kOrderOff;
-    else if (T == 16 && A == 1) s->order_mode = num_envs >= 32768 ? kOrderSort : kOrderOff;
+    else if (T == 16 && A == 1) s->order_mode = num_envs >= 16384 ? kOrderSort : kOrderOff;
   }
   s->lds_pad = 0;
   if (const char* e = getenv("MIGYM_LDS_PAD")) s->lds_pad = atoi(e) > 0 ? atoi(e) : 0;

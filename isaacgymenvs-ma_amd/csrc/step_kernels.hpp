@@ -441,6 +441,7 @@ __device__ __forceinline__ void env_step_item(
     if (valid && v.dof_actuation) const_cast<float*>(v.dof_actuation)[(size_t)nd * a + d] = tau;
   }
   t.ph_mark(14);
+  int key_con = -1;  // the ordering key's contacts (-1: the last substep's row count is the key)
   if constexpr (RP) {  // gym.simulate replaced by the injected post-simulate state
     const float* rr = rp.root_states ? rp.root_states : v.root_states;
     for (int q = t.tl; q < 13; q += T) L.st().root[q] = rr[(size_t)13 * ac + q];
@@ -462,6 +463,12 @@ __device__ __forceinline__ void env_step_item(
     t.template outputs<true>(L.st().sens,
                              (v.dof_force || tp.task_id == MG_TASK_HUMANOID) ? L.st().dforce : nullptr,
                              (valid && v.net_contact_forces) ? v.net_contact_forces + (size_t)3 * m->num_bodies * a : nullptr);
+    // the next launch's order (below): the contacts of the pose outputs() left in the tiles; nothing without an order.
+    // 16-lane teams only: the Humanoid ordered worse by it (32,768 envs: 43.5 -> 40.8 M env-steps/s; a third of its
+    // contacts are between geoms, which this count does not predict; profiles/r08/ab_zero_rows.txt)
+    if constexpr (T == 16) {
+      if (ord.wcnt || ord.cost) key_con = t.key_contacts();
+    }
     t.stage_state();
   }
   mg::wsync();
@@ -605,7 +612,17 @@ __device__ __forceinline__ void env_step_item(
       for (int q = t.tl; q < nd; q += T) v.dof_force[(size_t)nd * a + q] = L.st().dforce[q];
   }
   if (ord.wcnt || ord.cost) {  // the next launch's order: the unit's largest row count (an env's agents, a wave's envs)
+    // the rows the next step's first substep starts from, counted on the state this step leaves behind: three per
+    // contact at the post-step pose (none after a reset: the reset pose is above the ground) and the limit rows of
+    // the staged DOF positions (the reset's, after a reset).  The last substep's own count, one substep staler, where
+    // the contacts are not predicted (no ground_round model, the 32-lane teams, the replay instance)
     int rows = L.nrows;
+    if (key_con >= 0) {
+      const int lim = t.node > 0 ? t.key_limit_rows(L.st().dof[2 * (t.node - 1)]) : 0;
+      const int l1 = __popcll((__ballot(lim >= 1) >> t.tb) & mg::team_bits<T>());
+      const int l2 = __popcll((__ballot(lim >= 2) >> t.tb) & mg::team_bits<T>());
+      rows = 3 * (do_reset ? 0 : key_con) + l1 + l2;
+    }
     const int A = tp.num_agents > 1 ? tp.num_agents : 1;
     const int U = ord.wcnt ? A : ord.unit;
     if (U > 1) {

@@ -3160,6 +3160,55 @@ struct Team {
     }
   }
 
+  // ---------------------------------------------------------------- the work ordering's key (step_kernels.hpp)
+  // The contacts the next step's first substep will start from, counted at the pose fk() left in the tiles
+  // (outputs()'s): the ground candidates by collide()'s own tests for ground_round models (spheres and capsules: the
+  // bounding test, then one or two end points below contact_offset), one lane per geom, capped like the list; nothing
+  // is emitted.  Contacts between geoms are not predicted: the last substep's count stands in for them (none on Ant).
+  // -1: not a ground_round model
+  __device__ __forceinline__ int key_contacts() const {
+    if (!mt->ground_round) return -1;
+    const float off = p->contact_offset;
+    const int G = mt->ng, cap = p->max_contacts < MC ? p->max_contacts : MC;
+    int ground = 0;
+    for (int g0 = 0; g0 < G; g0 += T) {
+      const int g = g0 + tl;
+      float d0 = 1e30f, d1 = 1e30f;
+      if (g < G && (mt->gfil[g] & MG_COLLIDE_GROUND)) {
+        V3 c;
+        M3 Rg;
+        geom_world(g, &c, &Rg);
+        if (c.z - mt->gf[g][15] < off) {
+          const float* gs = mt->gf[g] + 12;
+          const float r = gs[0];
+          float z0 = c.z;
+          if (mt->gtype[g] == MG_GT_CAPSULE) {
+            const float az = Rg.m[2][2] * gs[1];
+            z0 = c.z - az;
+            d1 = (c.z + az) - r;
+          }
+          d0 = z0 - r;
+        }
+      }
+      ground += __popcll((__ballot(d0 < off) >> tb) & team_bits<T>()) + __popcll((__ballot(d1 < off) >> tb) & team_bits<T>());
+    }
+    int pairs = 0;
+    if constexpr (MP > 0) {
+      const int nc = s->ncon;
+      for (int c0 = 0; c0 < nc; c0 += T) {
+        const int c = c0 + tl;
+        pairs += __popcll((__ballot(c < nc && cside(c, 3) >= 0) >> tb) & team_bits<T>());
+      }
+    }
+    return (ground < cap ? ground : cap) + pairs;
+  }
+  // the limit rows build_rows() opens for this lane's DOF at position q (its comparisons)
+  __device__ __forceinline__ int key_limit_rows(float q) const {
+    if (!(node > 0 && mt->limited[node])) return 0;
+    const float* np = nprop(node);
+    return (q - np[4] < p->limit_margin ? 1 : 0) + (np[5] - q < p->limit_margin ? 1 : 0);
+  }
+
   // ---------------------------------------------------------------- state I/O (gym layouts)
   __device__ __forceinline__ void load(const float* root, const float* dof, const float* act_tau, const float* orow = nullptr,
                        const float* tg = nullptr) {

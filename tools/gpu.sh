@@ -12,7 +12,8 @@
 #   tools/gpu.sh stats OUT [BENCH ARGS...]      rocprofv3 --kernel-trace --stats of one bench command
 #   tools/gpu.sh pmc OUT Task N [obj] [VAR]     the four separate --pmc passes + tools/pmc_summary.py JSON
 #   tools/gpu.sh traffic OUT "VAR..." SPEC      FETCH_SIZE / WRITE_SIZE passes (and a bench line) per variant
-#   tools/gpu.sh phase OUT SPEC...              per-phase cycle profile (the --timing build)
+#   tools/gpu.sh phase OUT SPEC...              per-phase cycle profile (the --timing build; PHASE_ARGS="--pool 8":
+#                                               the benchmark's rollout)
 #   tools/gpu.sh multirank N                    torchrun x N ranks sharing the one GPU (gloo), both gather modes
 #   tools/gpu.sh profile R                      a round's kernel stats and PMC passes per kernel instance
 #   tools/gpu.sh lines R                        a round's bench lines of every config
@@ -121,7 +122,7 @@ case $mode in
     OUT=gpurun_out/${1:?out}; shift; mkdir -p "$OUT"
     for spec in "$@"; do
       IFS=: read -r t n o k <<< "$spec"; o=${o:-block}
-      timeout -k 10 240 python -u tools/phase_timing.py --task "$t" --num-envs "$n" --object-type "$o" \
+      timeout -k 10 240 python -u tools/phase_timing.py --task "$t" --num-envs "$n" --object-type "$o" ${PHASE_ARGS:-} \
         > "$OUT/phase_timing_${t}_${n}_$o.txt" 2>&1 || { echo "phase $spec failed"; exit 1; }
       echo "done $spec"
     done ;;

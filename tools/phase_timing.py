@@ -36,6 +36,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--object-type", default="block", help="ShadowHand objectType")
+    ap.add_argument("--pool", type=int, default=4,
+                    help="action tensors the rollout cycles through (bench.py cycles 8: --pool 8 is its rollout)")
     ap.add_argument("--per-wave", action="store_true",
                     help="launch by launch: the heaviest 1 %% of items (waves) against the mean item, per phase")
     args = ap.parse_args()
@@ -54,9 +56,9 @@ def main():
     env = migym.make(seed=0, task=args.task, num_envs=args.num_envs, sim_device="cuda:0", rl_device="cuda:0",
                      headless=True, **mk)
     g = torch.Generator(device="cuda:0").manual_seed(0)
-    acts = [torch.rand((env.num_actors, env.num_actions), device="cuda:0", generator=g) * 2 - 1 for _ in range(4)]
+    acts = [torch.rand((env.num_actors, env.num_actions), device="cuda:0", generator=g) * 2 - 1 for _ in range(args.pool)]
     for i in range(args.warmup):
-        env.step(acts[i % 4])
+        env.step(acts[i % args.pool])
     out = np.zeros(NPHASE, np.uint64)
     timing = lib.mg_debug_phase_cycles(out.ctypes.data, 1) == 0  # production build: wall clock only
     if args.per_wave:
@@ -67,7 +69,7 @@ def main():
     import time
     t0 = time.perf_counter()
     for i in range(args.steps):
-        env.step(acts[i % 4])
+        env.step(acts[i % args.pool])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if not timing:
@@ -103,7 +105,7 @@ def per_wave(args, env, lib, acts, out):
     show = [i for i in NAMES if i != 13]
     for k in range(args.steps):
         _abi.check(lib.mg_debug_phase_cycles(out.ctypes.data, 1), lib)
-        env.step(acts[k % 4])
+        env.step(acts[k % args.pool])
         torch.cuda.synchronize()
         _abi.check(lib.mg_debug_phase_waves(rows.ctypes.data, items), lib)
         r = rows.astype(np.float64)
