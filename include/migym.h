@@ -12,6 +12,9 @@
  *   mg_sim_bind          gym.acquire_*_tensor + gymtorch.wrap_tensor
  *                                                   (tasks/ant.py:78-95, humanoid.py:75-95)
  *   mg_sim_simulate      gym.simulate(sim)          (tasks/base/vec_task.py:381-384)
+ *   mg_sim_set_link_forces
+ *                        gym.apply_rigid_body_force_tensors on articulation links
+ *                                                   (tasks/quadcopter.py:330)
  *   mg_set_indexed       gym.set_actor_root_state_tensor_indexed /
  *                        gym.set_dof_state_tensor_indexed
  *                                                   (tasks/ant.py:265-271, cartpole.py:153-155)
@@ -195,8 +198,10 @@ typedef struct mg_state_views {
   const float* dof_targets; /* (N*A*nD) PD position targets (set_dof_position_target_tensor), may be NULL */
   /* gym.apply_rigid_body_force_tensors(sim, forces, None, space) (shadow_hand.py:700-708): forces
    * (N*A*nB, 3) in the rigid-body layout, applied at each body's centre of mass for every substep
-   * of the next simulate.  Rows of the free object are applied; articulation rows must be zero.
-   * NULL = no forces.  The fused hand step writes this tensor (it owns the random-force update). */
+   * of the next simulate.  Rows of the free object are applied.  Articulation rows are applied by
+   * mg_sim_simulate once mg_sim_set_link_forces(sim, 1) is set (objectless models; below) and must be zero
+   * otherwise: they are not read.  NULL = no forces.  The fused hand step writes this tensor (it owns the
+   * random-force update). */
   float* rb_forces;
   int32_t rb_force_space;   /* MG_LOCAL_SPACE: body frame at the start of each substep; else world */
   int32_t env_props_stride; /* floats per row of env_props (mg_env_props_layout) */
@@ -457,6 +462,15 @@ int mg_sim_create(const mg_model* model, const mg_sim_params* params, int32_t nu
                   mg_sim** out);
 int mg_sim_bind(mg_sim* sim, const mg_state_views* views);
 int mg_sim_simulate(mg_sim* sim, void* stream);
+/* Link forces (gym.apply_rigid_body_force_tensors on articulation links; torques are not built).  enable != 0: every
+ * mg_sim_simulate reads each articulation row of the bound views.rb_forces ((N*A*nB, 3), nB = model.num_bodies) and
+ * applies it at that body's centre of mass in every substep, in views.rb_force_space (MG_LOCAL_SPACE: the body's
+ * frame of each substep's own start; else the env frame).  The tensor is read at every simulate and never cleared.
+ * The launch then takes instances of its own, in the classic team layout at every batch size, and
+ * mg_sim_simulate fails (nothing launched or written) with a NULL rb_forces, a model with a free object, env_props
+ * bound, the compact layout pinned, or more bodies than the instance has nodes; mg_env_step and mg_env_step_replay
+ * fail while it is on.  enable == 0 (the default): exactly the behaviour without this call. */
+int mg_sim_set_link_forces(mg_sim* sim, int32_t enable);
 int mg_sim_destroy(mg_sim* sim);
 
 /* Scatter rows of `src` (same layout as the bound buffer) into the bound
@@ -713,6 +727,68 @@ int mg_anymal_post(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_view
  * mg_reset_idx. */
 int mg_anymal_reset_idx(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* views,
                         const mg_task_buffers* tb, const int32_t* ids, int32_t n, void* stream);
+
+/* ---- Quadcopter (quadcopter.py): the thrust-driven quadcopter as three launches per control step --
+ * mg_quadcopter_pre, mg_sim_simulate x controlFrequencyInv with link forces on (mg_sim_set_link_forces), and
+ * mg_quadcopter_post -- all asynchronous on the caller's stream, no host synchronisation, no atomics.  One free-base
+ * 8-DOF, 9-body articulation per env (migym.model.quadcopter_model), every DOF on a position drive; the sim must have
+ * dof_targets and rb_forces bound (MG_LOCAL_SPACE).  New structs only; mg_task_buffers is reused for the VecTask
+ * buffers. */
+#define MG_QUAD_DOFS 8
+#define MG_QUAD_BODIES 9
+#define MG_QUAD_OBS 21
+#define MG_QUAD_ACTIONS 12
+#define MG_QUAD_NOISE_COLS 11
+typedef struct mg_quadcopter_params {
+  /* dt * 8 pi and dt * 200 (quadcopter.py:310-315), each product taken in double on the host (dt the C float that
+   * gymapi.SimParams.dt is) and rounded to fp32 once, as a Python float times a tensor is */
+  float dof_step, thrust_step;
+  float dof_lower[MG_QUAD_DOFS], dof_upper[MG_QUAD_DOFS];
+  float thrust_lower, thrust_upper;           /* 0 and max_thrust = 2 (quadcopter.py:87-89) */
+  float init_root[13];                        /* initial_root_states row */
+  float init_dof[2 * MG_QUAD_DOFS];           /* initial_dof_states row: (pos, vel) per DOF */
+  float clip_actions, clip_obs;
+  int32_t max_episode_length;
+  int32_t rotor_body[4];                      /* rows of the force tensor that carry the thrusts (2, 4, 6, 8) */
+} mg_quadcopter_params;
+
+/* task-owned device tensors */
+typedef struct mg_quadcopter_views {
+  float* thrusts;                             /* (N, 4) */
+  float* dof_targets;                         /* (N*8): the buffer the sim has bound as dof_targets */
+  float* forces;                              /* (N, 9, 3): the buffer the sim has bound as rb_forces */
+} mg_quadcopter_views;
+size_t mg_quadcopter_params_sizeof(void);
+size_t mg_quadcopter_views_sizeof(void);
+
+/* mg_task_buffers fields the Quadcopter entry points use: actions (N, 12), actions_out, obs (N, 21), obs_clamped, rew,
+ * reset, progress, timeout, noise, seed, step_counter, env_offset, out_pack.  noise: (N, 11) U(0,1) per env in the
+ * reference's draw order [x | y | z | dof position 8] (quadcopter.py:289-294), mapped as torch_rand_float does,
+ * (upper - lower) * u + lower; NULL = the counter RNG keyed by (seed, env_offset + env, step_counter, column). */
+
+/* pre_physics_step (quadcopter.py:301-330), one launch, per env, in the reference's order: an env with reset != 0 is
+ * reset first (DOF state and root row from the initial state, x, y += U(-1.5, 1.5), z += U(-0.2, 1.5), DOF positions
+ * U(-0.2, 0.2), velocities 0, reset = 0, progress = 0); actions_out = clamp(actions, +-clip_actions); targets +=
+ * dof_step * a[0:8], clamped to the DOF limits; thrusts += thrust_step * a[8:12], clamped to [thrust_lower,
+ * thrust_upper]; forces[rotor_body[k]][2] = thrusts[k]; for the envs just reset thrusts = 0, their force rows = 0 and
+ * targets = the new DOF positions.  Products, then sums: no FMA. */
+int mg_quadcopter_pre(mg_sim* sim, const mg_quadcopter_params* qp, const mg_quadcopter_views* views,
+                      const mg_task_buffers* tb, void* stream);
+
+/* post_physics_step + the VecTask.step tail (quadcopter.py:332-418), one launch, per env: progress += 1;
+ * observations [(target - pos) / 3 | quat | linvel / 2 | angvel / pi | dof pos], target (0, 0, 1);
+ * compute_quadcopter_reward (reset on target_dist > 3, z < 0.3, or progress >= max_episode_length - 1); timeout, the
+ * observation clamp, out_pack.  state: NULL = the sim's bound views; else its root_states and dof_state are taken as the
+ * post-simulate state (physics-free replay). */
+int mg_quadcopter_post(mg_sim* sim, const mg_quadcopter_params* qp, const mg_quadcopter_views* views,
+                       const mg_task_buffers* tb, const mg_state_views* state, void* stream);
+
+/* reset_idx(env_ids) now (quadcopter.py:280-299): the n listed envs get the state reset of mg_quadcopter_pre (not its
+ * clearing of thrusts, forces and targets, which pre_physics_step does), reset = 0 and progress = 0; a repeated id
+ * writes the same values twice, an id outside 0..N-1 is skipped.  Noise: tb->noise rows by env, or the counter RNG on
+ * the manual-reset stream (step_counter | 2^62), as mg_reset_idx. */
+int mg_quadcopter_reset_idx(mg_sim* sim, const mg_quadcopter_params* qp, const mg_quadcopter_views* views,
+                            const mg_task_buffers* tb, const int32_t* ids, int32_t n, void* stream);
 
 /* ---- Rendering (VecTask.render under virtual_screen_capture, tasks/base/vec_task.py render): a pinhole ray caster
  * over the envs' collision geometry, two launches on the caller's stream, no host synchronisation.  The image shows

@@ -4,6 +4,8 @@
     hipcc -O3 --offload-arch=gfx950 -c csrc/inst.hip -DMG_INST=i  (team kernels, one capacity instance
                                                                     per object, i < MG_NUM_INST)
     hipcc ... -c csrc/inst.hip -DMG_INST=i -DMG_CONTACTS_TU       (the instance's contact read-out, tests only)
+    hipcc ... -c csrc/inst.hip -DMG_INST=i -DMG_LINKFORCE_TU      (k_simulate with link forces: the objectless
+                                                                    instances in the classic layout)
     hipcc -shared *.o -> migym/_lib/libmigym.so
 
 The objects compile in parallel (one process per translation unit, at most MIGYM_JOBS / os.cpu_count()).
@@ -30,6 +32,15 @@ ARCH = os.environ.get("MIGYM_ARCH", "gfx950")
 def num_instances():
     txt = open(os.path.join(CSRC, "dispatch.hpp")).read()
     return int(re.search(r"#define MG_NUM_INST (\d+)", txt).group(1))
+
+
+def linkforce_instances():
+    """the instances of MG_INSTANCES (dispatch.hpp) without a free object and in the classic layout"""
+    txt = open(os.path.join(CSRC, "dispatch.hpp")).read()
+    body = txt[txt.index("#define MG_INSTANCES(X)"):txt.index("#define MG_NUM_INST")]
+    rows = [[f.strip() for f in r.split(",")] for r in re.findall(r"\bX\(([^)]*)\)", body)]
+    assert len(rows) == num_instances(), "build.py: MG_INSTANCES does not parse"
+    return [i for i, r in enumerate(rows) if r[5] == "0" and r[6] == "0"]
 
 
 def needs_build(out=OUT):
@@ -98,6 +109,13 @@ def build(force=False, verbose=False, timing=False, variant=None, defines=(), ex
         if j >= ninst:
             inst.append("-DMG_CONTACTS_TU")
         cmds.append([hipcc] + flags + inst + ["-c", "-o", o, src])
+        objs.append(o)
+    # ... and after them the link-force variants of k_simulate (-DMG_LINKFORCE_TU, mg_sim_set_link_forces): the
+    # objectless instances in the classic layout, again in code objects of their own
+    for i in linkforce_instances():
+        o = os.path.join(objdir, f"linkforce{i}.o")
+        cmds.append([hipcc] + flags + [f"-DMG_INST={i}", "-mllvm", "-disable-machine-licm", "-mllvm", "-enable-ipra=false",
+                                       "-DMG_LINKFORCE_TU", "-c", "-o", o, INST])
         objs.append(o)
     _run_parallel(cmds, verbose)
     subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out + ".tmp"] + objs)

@@ -56,7 +56,11 @@ struct mg_sim {
   // otherwise) and the tensors mg_dynamics_bind bound
   void* d_dyn;
   mg_dynamics_views dyn;
+  // mg_sim_set_link_forces: mg_sim_simulate applies every articulation row of views.rb_forces (k_simulate_xf)
+  bool link_forces;
 };
+// layout_n under MIGYM_LAYOUT=compact: a batch past every threshold
+constexpr long kLayoutCompact = 1L << 40;
 
 // the step kernels' ordering arguments: the bucket lists this launch reads (rcnt nullptr: slot = env) and writes
 // (wcnt nullptr: no ordering), the read set's counts the last wave clears, the finished-wave counter

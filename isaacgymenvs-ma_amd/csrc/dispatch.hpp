@@ -50,6 +50,22 @@ template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY>
 struct RunContacts {
   static int run(hipStream_t s, const mg_sim* sim, float* out, int32_t* count, int32_t cap);
 };
+// gym.simulate with link forces (k_simulate_xf; mg_sim_set_link_forces): the objectless capacities in the classic
+// layout, in translation units of their own (inst.hip -DMG_LINKFORCE_TU)
+template <int T, int MN, int MC, int MG, int MP>
+struct RunSimulateXF {
+  static int run(hipStream_t s, const mg_sim* sim);
+};
+// ... as a dispatch functor: the instances it has none for refuse
+template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY>
+struct SimulateXF {
+  static int run(hipStream_t s, const mg_sim* sim) {
+    if constexpr (OBJ != 0 || LAY != 0)
+      return fail(MG_EINVAL, "mg_sim_simulate: link forces have no object / hand instance and none in the compact layout");
+    else
+      return RunSimulateXF<T, MN, MC, MG, MP>::run(s, sim);
+  }
+};
 // phase-timing build: publish the per-wave accumulator buffer to instance I's code object
 template <int I>
 int phase_buf_publish(unsigned long long* buf);

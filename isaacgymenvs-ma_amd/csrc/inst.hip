@@ -2,6 +2,7 @@
 // file once per -DMG_INST=i, i < MG_NUM_INST, in parallel, and links the objects with migym.hip).
 // With -DMG_CONTACTS_TU the unit holds the instance's contact read-out alone (k_contacts, mg_debug_contacts: tests
 // only) -- a code object of its own, so that the shipped instances' code objects are what they are without it.
+// With -DMG_LINKFORCE_TU it holds the instance's k_simulate with link forces alone (k_simulate_xf), likewise.
 #include "step_kernels.hpp"
 
 #ifndef MG_INST
@@ -11,7 +12,10 @@ static_assert(MG_INST >= 0 && MG_INST < MG_NUM_INST, "MG_INST out of range");
 
 namespace mgi {
 constexpr InstDesc kI = kInst[MG_INST];
-#ifdef MG_CONTACTS_TU
+#if defined(MG_LINKFORCE_TU)
+static_assert(kI.OBJ == 0 && kI.LAY == 0, "link forces: the objectless instances in the classic layout (build.py)");
+template struct RunSimulateXF<kI.T, kI.MN, kI.MC, kI.MG, kI.MP>;
+#elif defined(MG_CONTACTS_TU)
 template struct RunContacts<kI.T, kI.MN, kI.MC, kI.MG, kI.MP, kI.OBJ, kI.LAY>;
 #else
 template struct BuildTile<kI.T, kI.MN, kI.MC, kI.MG, kI.MP, kI.OBJ, kI.LAY>;

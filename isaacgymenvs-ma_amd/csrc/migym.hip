@@ -13,6 +13,7 @@
 #include "render.hpp"
 #include "anymal_task.hpp"  // as reach_task.hpp: restores FMA contraction at its end
 #include "amp_task.hpp"     // likewise
+#include "quadcopter_task.hpp"  // likewise
 #include "reach_task.hpp"   // before hand_task.hpp: that header leaves FMA contraction off for the rest of this file
 #include "hand_task.hpp"
 #include "task.hpp"
@@ -584,6 +585,7 @@ int mg_sim_create(const mg_model* model, const mg_sim_params* params, int32_t nu
   s->n = num_envs;
   s->device = device;
   s->bound = false;
+  s->link_forces = false;
   if (hipMalloc(&s->d_model, sizeof(mg_model)) != hipSuccess) {
     delete s;
     return fail(MG_ENOMEM, "mg_sim_create: hipMalloc(model) failed");
@@ -634,7 +636,7 @@ int mg_sim_create(const mg_model* model, const mg_sim_params* params, int32_t nu
   s->layout_n = s->n;
   if (const char* e = getenv("MIGYM_LAYOUT")) {
     if (!strcmp(e, "classic")) s->layout_n = 0;
-    else if (!strcmp(e, "compact")) s->layout_n = 1L << 40;
+    else if (!strcmp(e, "compact")) s->layout_n = kLayoutCompact;
     else if (strcmp(e, "auto")) {
       mg_sim_destroy(s);
       return fail(MG_EINVAL, "mg_sim_create: MIGYM_LAYOUT must be auto, compact or classic");
@@ -715,10 +717,28 @@ int mg_sim_bind(mg_sim* sim, const mg_state_views* views) {
 
 int mg_sim_simulate(mg_sim* sim, void* stream) {
   if (!sim || !sim->bound) return fail(MG_EINVAL, "mg_sim_simulate: sim not bound");
+  if (sim->link_forces) {
+    // link forces (mg_sim_set_link_forces): the classic layout's own instances at every batch size
+    if (!sim->views.rb_forces) return fail(MG_EINVAL, "mg_sim_simulate: link forces are on and no rb_forces tensor is bound");
+    if (sim->views.env_props)
+      return fail(MG_EINVAL, "mg_sim_simulate: link forces have no domain-randomized instance (env_props is bound)");
+    if (sim->layout_n >= kLayoutCompact)
+      return fail(MG_EINVAL, "mg_sim_simulate: link forces have no instance in the compact layout (MIGYM_LAYOUT=compact)");
+    int rc = mgi::dispatch<mgi::SimulateXF>(sim->host_model, sim->params.max_contacts, 0L, (hipStream_t)stream,
+                                            (const mg_sim*)sim);
+    if (rc) return rc;
+    return check_launch("mg_sim_simulate");
+  }
   int rc = mgi::dispatch<mgi::RunSimulate>(sim->host_model, sim->params.max_contacts, sim->layout_n, (hipStream_t)stream,
                                  (const mg_sim*)sim);
   if (rc) return rc;
   return check_launch("mg_sim_simulate");
+}
+
+int mg_sim_set_link_forces(mg_sim* sim, int32_t enable) {
+  if (!sim) return fail(MG_EINVAL, "mg_sim_set_link_forces: bad arguments");
+  sim->link_forces = enable != 0;
+  return MG_OK;
 }
 
 // Tests only: the contact list the first substep of mg_sim_simulate would build from the bound state (k_contacts,
@@ -1101,6 +1121,9 @@ static int env_step(mg_sim* sim, const mg_task_params* tp, const mg_task_buffers
   if (!sim || !sim->bound || !tp || !tb || !tb->actions || !tb->obs || !tb->rew || !tb->reset || !tb->progress ||
       !tb->timeout)
     return fail(MG_EINVAL, "mg_env_step: bad arguments");
+  if (sim->link_forces)
+    return fail(MG_EINVAL, rp ? "mg_env_step_replay: the fused step applies no link forces (mg_sim_set_link_forces is on)"
+                              : "mg_env_step: the fused step applies no link forces (mg_sim_set_link_forces is on)");
   const bool hand = tp->task_id == MG_TASK_SHADOW_HAND;
   if (hand != (sim->host_model.obj_type != 0))
     return fail(MG_EINVAL, "mg_env_step: ShadowHand needs a model with a free object (and only it does)");
@@ -1438,6 +1461,67 @@ int mg_anymal_reset_idx(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal
   hipLaunchKernelGGL(mga::k_anymal_reset_idx, dim3((n + mga::kEnvs - 1) / mga::kEnvs), dim3(64), 0,
                      (hipStream_t)stream, *ap, *views, t, st, ids, n, sim->n);
   return check_launch("mg_anymal_reset_idx");
+}
+
+// ---- Quadcopter: the task layer around mg_sim_simulate with link forces (quadcopter_task.hpp)
+size_t mg_quadcopter_params_sizeof(void) { return sizeof(mg_quadcopter_params); }
+size_t mg_quadcopter_views_sizeof(void) { return sizeof(mg_quadcopter_views); }
+
+// the shared argument check: a bound free-base sim of 8 DOFs and 9 bodies, the rotor rows inside the force tensor
+static int quadcopter_args_ok(const mg_sim* sim, const mg_quadcopter_params* qp, const mg_quadcopter_views* v,
+                              const mg_task_buffers* tb, const char* who) {
+  if (!sim || !qp || !v || !tb) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
+  if (!sim->bound) return fail(MG_EINVAL, std::string(who) + ": sim not bound");
+  const mg_model& m = sim->host_model;
+  if (m.fixed_base || m.obj_type || m.num_nodes - 1 != MG_QUAD_DOFS || m.num_bodies != MG_QUAD_BODIES)
+    return fail(MG_EINVAL, std::string(who) + ": needs a free-base model of 8 DOFs and 9 bodies without a free object");
+  for (int k = 0; k < 4; k++)
+    if (qp->rotor_body[k] < 0 || qp->rotor_body[k] >= MG_QUAD_BODIES)
+      return fail(MG_EINVAL, std::string(who) + ": rotor_body out of range");
+  if (!v->thrusts || !v->dof_targets || !v->forces)
+    return fail(MG_EINVAL, std::string(who) + ": needs thrusts, dof_targets and forces");
+  if (!sim->views.root_states || !sim->views.dof_state)
+    return fail(MG_EINVAL, std::string(who) + ": needs root_states and dof_state");
+  return MG_OK;
+}
+
+int mg_quadcopter_pre(mg_sim* sim, const mg_quadcopter_params* qp, const mg_quadcopter_views* views,
+                      const mg_task_buffers* tb, void* stream) {
+  if (int rc = quadcopter_args_ok(sim, qp, views, tb, "mg_quadcopter_pre")) return rc;
+  if (!tb->actions || !tb->reset || !tb->progress) return fail(MG_EINVAL, "mg_quadcopter_pre: needs actions, reset and progress");
+  if (sim->views.dof_targets != views->dof_targets || sim->views.rb_forces != views->forces)
+    return fail(MG_EINVAL, "mg_quadcopter_pre: views.dof_targets / forces are not the buffers the sim has bound as "
+                           "dof_targets / rb_forces");
+  if (sim->n == 0) return MG_OK;
+  hipLaunchKernelGGL(mgq::k_quad_pre, dim3((sim->n + mgq::kEnvs - 1) / mgq::kEnvs), dim3(64), 0, (hipStream_t)stream,
+                     *qp, *views, *tb, sim->views.root_states, sim->views.dof_state, sim->n);
+  return check_launch("mg_quadcopter_pre");
+}
+
+int mg_quadcopter_post(mg_sim* sim, const mg_quadcopter_params* qp, const mg_quadcopter_views* views,
+                       const mg_task_buffers* tb, const mg_state_views* state, void* stream) {
+  if (int rc = quadcopter_args_ok(sim, qp, views, tb, "mg_quadcopter_post")) return rc;
+  if (!tb->obs || !tb->rew || !tb->reset || !tb->progress || !tb->timeout)
+    return fail(MG_EINVAL, "mg_quadcopter_post: needs obs, rew, reset, progress and timeout");
+  const mg_state_views& s = state ? *state : sim->views;
+  if (!s.root_states || !s.dof_state) return fail(MG_EINVAL, "mg_quadcopter_post: needs root_states and dof_state");
+  if (sim->n == 0) return MG_OK;
+  hipLaunchKernelGGL(mgq::k_quad_post, dim3((sim->n + mgq::kEnvs - 1) / mgq::kEnvs), dim3(64), 0, (hipStream_t)stream,
+                     *qp, *tb, (const float*)s.root_states, (const float*)s.dof_state, sim->n);
+  return check_launch("mg_quadcopter_post");
+}
+
+int mg_quadcopter_reset_idx(mg_sim* sim, const mg_quadcopter_params* qp, const mg_quadcopter_views* views,
+                            const mg_task_buffers* tb, const int32_t* ids, int32_t n, void* stream) {
+  if (int rc = quadcopter_args_ok(sim, qp, views, tb, "mg_quadcopter_reset_idx")) return rc;
+  if (n < 0 || (n > 0 && !ids) || !tb->reset || !tb->progress)
+    return fail(MG_EINVAL, "mg_quadcopter_reset_idx: bad arguments");
+  if (n == 0 || sim->n == 0) return MG_OK;
+  mg_task_buffers t = *tb;
+  t.step_counter = tb->step_counter | (1ull << 62);   // the manual-reset stream of the counter RNG, as mg_reset_idx
+  hipLaunchKernelGGL(mgq::k_quad_reset_idx, dim3((n + mgq::kEnvs - 1) / mgq::kEnvs), dim3(64), 0, (hipStream_t)stream,
+                     *qp, t, sim->views.root_states, sim->views.dof_state, ids, n, sim->n);
+  return check_launch("mg_quadcopter_reset_idx");
 }
 
 // ---- Rendering: the ray caster over the collision geometry (render.hpp)

@@ -72,12 +72,13 @@ static __device__ unsigned long long* g_phase_buf;
 // when a wave finishes (a block's slots free only when its slowest wave is done).  W is the smallest
 // of 1, 2, 4, 8 that reaches the most resident waves per CU (at most 4 x the instance's waves per SIMD: 8 at the
 // 256-register budget, 12 at 168).
-template <int T, int MN, int MC, int MG, int MP, int OBJ, bool DR, int LAY = 0>
+// XB: further LDS bytes per team that the kernel declares beside the slots (k_simulate_xf's force rows)
+template <int T, int MN, int MC, int MG, int MP, int OBJ, bool DR, int LAY = 0, int XB = 0>
 struct Shape {
   using TL = mg::TeamLDSOf<T, MN, MC, OBJ, MG, MP, LAY>;
   static constexpr int E1 = 64 / T;  // teams (actors) per wave
   static constexpr size_t kTile = sizeof(mg::ModelTile<MN, MG, MP, mg::tile_hull_verts(OBJ)>);
-  static constexpr size_t kWave = E1 * (sizeof(mg::BankSlot<TL, T>) + (DR ? sizeof(mg::DrTile<MN, MG>) : 0));
+  static constexpr size_t kWave = E1 * (sizeof(mg::BankSlot<TL, T>) + (DR ? sizeof(mg::DrTile<MN, MG>) : 0) + XB);
   static constexpr int fit(int w, int cap) {  // resident waves per CU with w-wave blocks, at most cap
     const size_t blk = (kTile + w * kWave + 511) / 512 * 512;
     const int b = (int)((160 * 1024) / blk);
@@ -207,6 +208,59 @@ __global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, OBJ, DR, LAY>::kThreads))
       for (int b = t.tl; b < nb; b += T) t.body_state(b, rb + 13 * b);
       if (OBJ)
         for (int k = t.tl; k < 26; k += T) rb[13 * nb + k] = k < 13 ? L.oroot[k] : root[26 + k - 13];
+    }
+  }
+}
+
+// gym.simulate with link forces (mg_sim_set_link_forces): k_simulate's objectless, non-DR instance in the classic
+// layout, with every articulation row of rb_forces applied at its body's centre of mass in every substep
+// (Team::aba(), XF).  The actor's rows are loaded once, over consecutive addresses, into the team's LDS rows;
+// Team::bind_xf() turns each into [force | COM in the node's frame], and the substeps read nothing else.
+template <int T, int MN, int MC, int MG, int MP, bool TGS = false>
+__global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>::kWPE))) void k_simulate_xf(
+    const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n) {
+  using SH = Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>;
+  constexpr int E = SH::E;
+  __shared__ mg::BankSlot<mg::TeamLDSOf<T, MN, MC, 0, MG, MP, 0>, T> lds[E];
+  __shared__ typename mg::Team<T, MN, MC, MG, MP, 0>::MT tile;
+  __shared__ float xf[E][6 * MN];
+  mg::copy_tile(&tile, static_cast<const typename mg::Team<T, MN, MC, MG, MP, 0>::MT*>(timg));
+  __syncthreads();
+  const int team = threadIdx.x / T;
+  const int a = blockIdx.x * E + team;
+  const bool valid = a < n;
+  const int ac = valid ? a : n - 1;
+  const int nd = m->num_dofs, ns = m->num_sensors, nb = m->num_bodies;  // nb <= MN (RunSimulateXF)
+  mg::Team<T, MN, MC, MG, MP, 0, TGS, 0, true> t;
+  t.init(&lds[team].v, &tile, m, &p);
+  {
+    const float* fr = v.rb_forces + (size_t)3 * nb * ac;
+    for (int k = t.tl; k < 3 * nb; k += T) xf[team][k] = fr[k];
+    mg::wsync();
+    const mg::V3 f = t.tl < nb ? mg::ld3(&xf[team][3 * t.tl]) : mg::v3(0.0f, 0.0f, 0.0f);
+    mg::wsync();  // every lane holds its row: bind_xf() overwrites them
+    t.bind_xf(xf[team], f, v.rb_force_space == MG_LOCAL_SPACE);
+  }
+  float* root = v.root_states + (size_t)13 * ac;
+  t.load(root, v.dof_state + (size_t)2 * nd * ac, v.dof_actuation ? v.dof_actuation + (size_t)nd * ac : nullptr, nullptr,
+         v.dof_targets ? v.dof_targets + (size_t)nd * ac : nullptr);
+  for (int st = 0; st < p.substeps; st++) t.substep();
+  t.outputs(lds[team].v.st().sens, lds[team].v.st().dforce,
+            (valid && v.net_contact_forces) ? v.net_contact_forces + (size_t)3 * nb * a : nullptr);
+  t.stage_state();
+  mg::wsync();
+  if (valid) {
+    auto& L = lds[team].v;
+    if (!m->fixed_base)
+      for (int k = t.tl; k < 13; k += T) root[k] = L.st().root[k];
+    for (int k = t.tl; k < 2 * nd; k += T) v.dof_state[(size_t)2 * nd * a + k] = L.st().dof[k];
+    if (v.sensors)
+      for (int k = t.tl; k < 6 * ns; k += T) v.sensors[(size_t)6 * ns * a + k] = L.st().sens[k];
+    if (v.dof_force)
+      for (int k = t.tl; k < nd; k += T) v.dof_force[(size_t)nd * a + k] = L.st().dforce[k];
+    if (v.rigid_body_states) {
+      float* rb = v.rigid_body_states + (size_t)13 * nb * a;
+      for (int b = t.tl; b < nb; b += T) t.body_state(b, rb + 13 * b);
     }
   }
 }
@@ -1087,6 +1141,22 @@ int RunSimulate<T, MN, MC, MG, MP, OBJ, LAY>::run(hipStream_t s, const mg_sim* s
     launch<Shape<T, MN, MC, MG, MP, OBJ, false, LAY>>(k_simulate<T, MN, MC, MG, MP, OBJ, false, false, LAY>, s, sim->n, sim->d_model,
                                                   (const void*)sim->d_tile, sim->params, sim->views, sim->n);
   }
+  return MG_OK;
+}
+
+template <int T, int MN, int MC, int MG, int MP>
+int RunSimulateXF<T, MN, MC, MG, MP>::run(hipStream_t s, const mg_sim* sim) {
+  if (!sim->d_tile) return fail(MG_ECAPACITY, "mg_sim_simulate: no model tile (model exceeds every kernel instance)");
+  // one LDS row and one lane per body (Team::bind_xf)
+  if (sim->host_model.num_bodies > MN)
+    return fail(MG_ECAPACITY, "mg_sim_simulate: link forces: the model has more bodies than its kernel instance has nodes");
+  using SH = Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>;
+  if (sim->params.solver_type == MG_SOLVER_TGS)
+    launch<SH>(k_simulate_xf<T, MN, MC, MG, MP, true>, s, sim->n, sim->d_model, (const void*)sim->d_tile, sim->params,
+               sim->views, sim->n);
+  else
+    launch<SH>(k_simulate_xf<T, MN, MC, MG, MP, false>, s, sim->n, sim->d_model, (const void*)sim->d_tile, sim->params,
+               sim->views, sim->n);
   return MG_OK;
 }
 

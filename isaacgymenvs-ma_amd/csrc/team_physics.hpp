@@ -881,8 +881,20 @@ __device__ __forceinline__ bool box_box_edge(V3 c, const M3& R, V3 hg, V3 hb, fl
 // memory, and every phase then runs from scratch (egg: 7.4 -> 4.7 M env-steps/s until this was found).
 // OBJ: the free object's type (0: none); TGS: the build's TGS solver (mg_sim_params.solver_type) -- its
 // own kernel instances, so the PGS instances are the code they were
-template <int T, int MN, int MC, int MG, int MP, int OBJ = 0, bool TGS = false, int LAY = 0>
-struct Team {
+// XF: link forces (mg_sim_set_link_forces; bind_xf() below, applied in aba()) -- instances of their own again.  Their
+// state is an empty base otherwise: the hand kernels keep parts of the Team in memory, and a member more moved their code
+template <bool XF>
+struct TeamXf {};
+// the team's rows in LDS, one per body: [force | body COM in its node's frame]; the force in the world frame, or
+// (xfl: MG_LOCAL_SPACE) in the node's frame, so that aba() needs the node's own R and x alone
+template <>
+struct TeamXf<true> {
+  const float* xfr;
+  unsigned long long xfm;  // the bodies of this lane's node whose row is not zero
+  bool xfl;
+};
+template <int T, int MN, int MC, int MG, int MP, int OBJ = 0, bool TGS = false, int LAY = 0, bool XF = false>
+struct Team : TeamXf<XF> {
   using L = TeamLDSOf<T, MN, MC, OBJ, MG, MP, LAY>;
   using MT = ModelTile<MN, MG, MP, tile_hull_verts(OBJ)>;
   static constexpr int MR = L::MR;
@@ -966,6 +978,29 @@ struct Team {
   V3 op;
   float oq[4];
   M3 oR;
+
+  // link forces (XF, TeamXf): `f` is row tl of the actor's rb_forces (lanes tl < num_bodies <= T), `rows` the team's
+  // 6 num_bodies floats of LDS.  Once per launch: nothing here is read from global memory again in the substeps
+  __device__ __forceinline__ void bind_xf(float* rows, V3 f, bool local) {
+    static_assert(XF && MN <= T && MN <= 64, "bind_xf: one lane per body, one mask bit per body");
+    const int nb = m->num_bodies;
+    unsigned long long& xfm = this->xfm;
+    this->xfr = rows;
+    this->xfl = local;
+    int bn = -1;
+    if (tl < nb) {
+      const M3 Rq = quat_to_mat(m->body_quat[tl][0], m->body_quat[tl][1], m->body_quat[tl][2], m->body_quat[tl][3]);
+      const V3 c = ld3(m->body_pos[tl]) + mul(Rq, ld3(m->body_com[tl]));
+      const V3 fn = local ? mul(Rq, f) : f;
+      rows[6 * tl + 0] = fn.x; rows[6 * tl + 1] = fn.y; rows[6 * tl + 2] = fn.z;
+      rows[6 * tl + 3] = c.x; rows[6 * tl + 4] = c.y; rows[6 * tl + 5] = c.z;
+      if (f.x != 0.0f || f.y != 0.0f || f.z != 0.0f) bn = m->body_node[tl];
+    }
+    xfm = 0ull;
+    for (int b = 0; b < nb; b++)
+      if (__shfl(bn, tb + b) == node && node >= 0) xfm |= 1ull << b;
+    wsync();
+  }
 
   __device__ __forceinline__ int col_of(int i) const { return ncol0 - 1 + i; }
 
@@ -1124,6 +1159,13 @@ struct Team {
       SV IV = mul(IA, V);
       V3 mg = ld3(p->gravity) * (mass * gscale());
       pA = crf(V, IV) - sv(cross(cc, mg), mg);
+      if constexpr (XF) {  // link forces at the bodies' COMs, in this substep's frames (several bodies of a node add up)
+        for (unsigned long long bm = this->xfm; bm; bm &= bm - 1) {
+          const float* e = this->xfr + 6 * __builtin_ctzll(bm);
+          const V3 fw = this->xfl ? mul(R, ld3(e)) : ld3(e);
+          pA = pA - sv(cross(x + mul(R, ld3(e + 3)) - o, fw), fw);
+        }
+      }
       // link angular damping (gym AssetOptions.angular_damping, mg_model.link_ang_damping): the couple
       // -c I_w w, implicit: + c I_w w in the bias, + h c I_w in the link's rotational block, so a free
       // link's w decays by 1/(1 + h c) per substep and the test solves see the same M~

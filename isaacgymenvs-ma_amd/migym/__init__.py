@@ -12,6 +12,9 @@ from __future__ import annotations
 
 __version__ = "0.1.0"
 
+# gymapi.ENV_SPACE / LOCAL_SPACE: the frames VecTask.apply_rigid_body_force_tensors takes (include/migym.h MG_*_SPACE)
+ENV_SPACE, LOCAL_SPACE = 0, 1
+
 
 def make(seed: int, task: str, num_envs: int, sim_device: str, rl_device: str, graphics_device_id: int = -1,
          headless: bool = False, multi_gpu: bool = False, virtual_screen_capture: bool = False,

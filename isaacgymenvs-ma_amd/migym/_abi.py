@@ -179,6 +179,23 @@ class AnymalViews(C.Structure):
     _fields_ = [("commands", C.c_void_p), ("dof_targets", C.c_void_p)]
 
 
+MG_QUAD_DOFS, MG_QUAD_BODIES, MG_QUAD_OBS, MG_QUAD_ACTIONS, MG_QUAD_NOISE_COLS = 8, 9, 21, 12, 11
+
+
+class QuadcopterParams(C.Structure):
+    """mg_quadcopter_params: the constants of Quadcopter (taskdefs.quadcopter_params)."""
+    _fields_ = [("dof_step", C.c_float), ("thrust_step", C.c_float), ("dof_lower", C.c_float * MG_QUAD_DOFS),
+                ("dof_upper", C.c_float * MG_QUAD_DOFS), ("thrust_lower", C.c_float), ("thrust_upper", C.c_float),
+                ("init_root", C.c_float * 13), ("init_dof", C.c_float * (2 * MG_QUAD_DOFS)),
+                ("clip_actions", C.c_float), ("clip_obs", C.c_float), ("max_episode_length", C.c_int32),
+                ("rotor_body", C.c_int32 * 4)]
+
+
+class QuadcopterViews(C.Structure):
+    """mg_quadcopter_views: the task-owned device tensors of Quadcopter."""
+    _fields_ = [("thrusts", C.c_void_p), ("dof_targets", C.c_void_p), ("forces", C.c_void_p)]
+
+
 MG_AMP_DOFS, MG_AMP_BODIES, MG_AMP_OBS, MG_AMP_KEY_BODIES = 28, 15, 105, 4
 MG_AMP_FRAME_FLOATS, MG_AMP_MAX_OBS_STEPS, MG_AMP_NOISE_COLS = 113, 16, 3
 MG_AMP_INIT = {"Default": 0, "Start": 1, "Random": 2, "Hybrid": 3}   # HumanoidAMP.StateInit
@@ -240,6 +257,7 @@ EXPORTS = {
     "mg_sim_create": (C.c_int, [C.c_void_p, C.POINTER(SimParams), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "mg_sim_bind": (C.c_int, [C.c_void_p, C.POINTER(StateViews)]),
     "mg_sim_simulate": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mg_sim_set_link_forces": (C.c_int, [C.c_void_p, C.c_int32]),
     "mg_sim_destroy": (C.c_int, [C.c_void_p]),
     "mg_set_indexed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mg_compute_observations": (C.c_int, [C.POINTER(TaskParams), C.c_int32] + [C.c_void_p] * 10 + [C.c_void_p]),
@@ -289,6 +307,14 @@ EXPORTS = {
                                  C.POINTER(StateViews), C.c_void_p]),
     "mg_anymal_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(AnymalParams), C.POINTER(AnymalViews),
                                       C.POINTER(TaskBuffers), C.c_void_p, C.c_int32, C.c_void_p]),
+    "mg_quadcopter_params_sizeof": (C.c_size_t, []),
+    "mg_quadcopter_views_sizeof": (C.c_size_t, []),
+    "mg_quadcopter_pre": (C.c_int, [C.c_void_p, C.POINTER(QuadcopterParams), C.POINTER(QuadcopterViews),
+                                    C.POINTER(TaskBuffers), C.c_void_p]),
+    "mg_quadcopter_post": (C.c_int, [C.c_void_p, C.POINTER(QuadcopterParams), C.POINTER(QuadcopterViews),
+                                     C.POINTER(TaskBuffers), C.POINTER(StateViews), C.c_void_p]),
+    "mg_quadcopter_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(QuadcopterParams), C.POINTER(QuadcopterViews),
+                                          C.POINTER(TaskBuffers), C.c_void_p, C.c_int32, C.c_void_p]),
     "mg_amp_params_sizeof": (C.c_size_t, []),
     "mg_amp_views_sizeof": (C.c_size_t, []),
     "mg_amp_pre": (C.c_int, [C.c_void_p, C.POINTER(AmpParams), C.POINTER(AmpViews), C.POINTER(TaskBuffers),
@@ -327,7 +353,9 @@ def check_layout(lib):
              "mg_osc_args_sizeof": C.sizeof(OscArgs), "mg_reach_params_sizeof": C.sizeof(ReachParams),
              "mg_reach_views_sizeof": C.sizeof(ReachViews), "mg_anymal_params_sizeof": C.sizeof(AnymalParams),
              "mg_anymal_views_sizeof": C.sizeof(AnymalViews), "mg_render_args_sizeof": C.sizeof(RenderArgs),
-             "mg_amp_params_sizeof": C.sizeof(AmpParams), "mg_amp_views_sizeof": C.sizeof(AmpViews)}
+             "mg_amp_params_sizeof": C.sizeof(AmpParams), "mg_amp_views_sizeof": C.sizeof(AmpViews),
+             "mg_quadcopter_params_sizeof": C.sizeof(QuadcopterParams),
+             "mg_quadcopter_views_sizeof": C.sizeof(QuadcopterViews)}
     for fn, py in sizes.items():
         c = getattr(lib, fn)()
         if c != py:

@@ -300,6 +300,17 @@ TASKS["HumanoidAMP"] = {
     "task": {"randomize": False},
 }
 
+# Quadcopter (cfg/task/Quadcopter.yaml).  The reference writes its own MJCF at run time; migym builds the model from
+# the same dimensions (migym.model.quadcopter_model), so the task needs no asset.
+TASKS["Quadcopter"] = {
+    "name": "Quadcopter",
+    "env": {"numEnvs": 8192, "envSpacing": 1.25, "maxEpisodeLength": 500, "enableDebugVis": False,
+            "clipObservations": 5.0, "clipActions": 1.0, "enableCameraSensors": False},
+    "sim": _sim(dt=0.01, num_position_iterations=4, num_velocity_iterations=0, contact_offset=0.02, rest_offset=0.001,
+                bounce_threshold_velocity=0.2, max_depenetration_velocity=1000.0, contact_collection=0),
+    "task": {"randomize": False},
+}
+
 
 def resolve_default(default, arg):
     """``${resolve_default:d,x}`` (isaacgymenvs/__init__.py:11)."""

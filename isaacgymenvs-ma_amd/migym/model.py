@@ -967,6 +967,45 @@ def load_json(path) -> ModelSpec:
     return ModelSpec.from_json(path)
 
 
+def quadcopter_model(chassis_radius=0.1, chassis_thickness=0.03, chassis_density=50.0, arm_radius=0.01,
+                     arm_density=200.0, rotor_radius=0.04, rotor_thickness=0.01, rotor_density=1000.0,
+                     arm_angles_deg=(45.0, 135.0, 225.0, 315.0), joint_range_deg=30.0) -> ModelSpec:
+    """The quadcopter of the reference's Quadcopter task (tasks/quadcopter.py:121-202), which writes its own MJCF at
+    run time and ships no asset, built from the named dimensions: a chassis cylinder on a free joint, and on each of
+    four arms at arm_angles_deg a small sphere on a pitch hinge (about its y) carrying a rotor cylinder on a roll hinge
+    (about its x), every hinge limited to +-joint_range_deg; masses and inertias from the geoms' densities.  Bodies in
+    depth-first order: chassis, rotor_arm0, rotor0, rotor_arm1, ...  The table load_mjcf makes of the reference's
+    file (tests/golden/quadcopter.json) differs only by the six digits that file is written with."""
+    lim = math.radians(joint_range_deg)
+
+    def solid(gtype, size, density):
+        m, I = geom_mass_inertia(gtype, size, density)
+        return dict(mass=float(m), com=[0.0, 0.0, 0.0], inertia=_inertia6(I))
+
+    nodes = [Node("chassis", -1, JT_FREE, [0, 0, 0], [0, 0, 0, 1], [0, 0, 1], 0,
+                  **solid(GT_CYLINDER, [chassis_radius, 0.5 * chassis_thickness], chassis_density))]
+    bodies = [Body("chassis", 0, [0.0, 0.0, 0.0], [0.0, 0.0, 0.0, 1.0], -1, nodes[0].mass)]
+    geoms = [Geom("g0", GT_CYLINDER, 0, 0, [chassis_radius, 0.5 * chassis_thickness, 0.0], [0.0, 0.0, 0.0],
+                  [0.0, 0.0, 0.0, 1.0])]
+    dof_names = []
+    for i, deg in enumerate(arm_angles_deg):
+        ang, reach = math.radians(deg), chassis_radius + 0.25 * arm_radius
+        parts = (("rotor_arm", "rotor_pitch", 0, [reach * math.cos(ang), reach * math.sin(ang), 0.0],
+                  [0.0, 0.0, math.sin(0.5 * ang), math.cos(0.5 * ang)], [0.0, 1.0, 0.0], GT_SPHERE, [arm_radius],
+                  arm_density),
+                 ("rotor", "rotor_roll", len(nodes), [rotor_radius + 0.25 * arm_radius, 0.0, 0.0], [0.0, 0.0, 0.0, 1.0],
+                  [1.0, 0.0, 0.0], GT_CYLINDER, [rotor_radius, 0.5 * rotor_thickness], rotor_density))
+        for body, joint, parent, t, r0, axis, gtype, size, density in parts:
+            k = len(nodes)
+            nodes.append(Node(f"{joint}{i}", parent, JT_HINGE, t, r0, axis, k, lower=-lim, upper=lim, limited=1,
+                              **solid(gtype, size, density)))
+            bodies.append(Body(f"{body}{i}", k, [0.0, 0.0, 0.0], [0.0, 0.0, 0.0, 1.0], nodes[k].parent, nodes[k].mass))
+            geoms.append(Geom(f"g{k}", gtype, k, k, (list(size) + [0.0, 0.0])[:3], [0.0, 0.0, 0.0],
+                              [0.0, 0.0, 0.0, 1.0]))
+            dof_names.append(f"{joint}{i}")
+    return ModelSpec("quadcopter", 0, nodes, bodies, geoms, [], [], dof_names)
+
+
 def hand_object(kind: str) -> Dict:
     """The free object of ShadowHand's objectType (shadow_hand.py:86-100): block = cube_multicolor.urdf,
     egg = open_ai_assets/hand/egg.xml (ellipsoid), pen = open_ai_assets/hand/pen.xml (capsule).  Shipped

@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
+
 from . import _abi
 from . import model as M
 
@@ -340,6 +342,53 @@ def reach_params(cfg: dict, spec: M.ModelSpec) -> _abi.ReachParams:
     rp.cube_z_base = float(table_z + cube_heights / 2)                         # franka_reach_MA.py:693
     rp.cube_z_range = 0.5
     return rp
+
+
+# ---- Quadcopter (quadcopter.py): no fused-kernel task id and no table (M.quadcopter_model builds the model);
+# z = the default pose (quadcopter.py:236-237); 16 contacts: the (16, 9, 16, 16, 0) instance
+QUADCOPTER_MAX_CONTACTS = 16
+TASK_INFO["Quadcopter"] = (None, None, 21, 12, 1.0, QUADCOPTER_MAX_CONTACTS)
+RENDER_DEFAULTS["Quadcopter"] = dict(width=320, height=240, fov_deg=60.0, eye=(0.8, -0.8, 0.5), target=(0.0, 0.0, 0.0),
+                                     follow=True)
+QUADCOPTER_ROTOR_BODIES = (2, 4, 6, 8)   # quadcopter.py:193: the rows of the force tensor that carry the thrusts
+
+
+def quadcopter_spec(spec: M.ModelSpec = None) -> M.ModelSpec:
+    """The quadcopter as the reference's task configures it, on a copy (quadcopter.py:216-221, 239-246): every DOF on a
+    position drive of stiffness 1000 and damping 0 without an effort limit, no link angular damping, hinge rates
+    capped at 4 pi.  ``spec``: M.quadcopter_model() by default."""
+    import copy
+    spec = copy.deepcopy(spec) if spec is not None else M.quadcopter_model()
+    for n in spec.nodes[1:]:
+        n.stiffness, n.damping = 0.0, 0.0
+        n.drive_kp, n.effort_limit = 1000.0, float(np.finfo(np.float32).max)
+    spec.angular_damping = 0.0
+    spec.max_angular_velocity = 4.0 * math.pi
+    return spec
+
+
+def quadcopter_params(cfg: dict, spec: M.ModelSpec) -> _abi.QuadcopterParams:
+    """Quadcopter constants (quadcopter.py:43-89, 225-237, 310-315), computed where the reference computes them: the
+    two action speed scales times dt as products of Python floats in double, dt the C float gymapi.SimParams.dt is,
+    rounded to fp32 once (a Python float times a float tensor)."""
+    env = cfg["env"]
+    if spec.num_dofs != _abi.MG_QUAD_DOFS or len(spec.bodies) != _abi.MG_QUAD_BODIES or spec.fixed_base:
+        raise ValueError("Quadcopter needs the free-base 8-DOF, 9-body model (M.quadcopter_model)")
+    qp = _abi.QuadcopterParams()
+    dt = float(np.float32(cfg["sim"]["dt"]))
+    qp.dof_step, qp.thrust_step = dt * (8 * math.pi), dt * 200
+    lo, hi = dof_limits(spec)
+    for j in range(_abi.MG_QUAD_DOFS):
+        qp.dof_lower[j], qp.dof_upper[j] = lo[j], hi[j]
+    qp.thrust_lower, qp.thrust_upper = 0.0, 2.0
+    for c, x in enumerate([0.0, 0.0, TASK_INFO["Quadcopter"][4], 0.0, 0.0, 0.0, 1.0] + [0.0] * 6):
+        qp.init_root[c] = x
+    qp.clip_actions = float(env.get("clipActions", math.inf))
+    qp.clip_obs = float(env.get("clipObservations", math.inf))
+    qp.max_episode_length = int(env["maxEpisodeLength"])
+    for k, b in enumerate(QUADCOPTER_ROTOR_BODIES):
+        qp.rotor_body[k] = b
+    return qp
 
 
 # ---- Anymal (anymal.py)

@@ -5,6 +5,7 @@ from .shadow_hand import ShadowHand
 from .franka_reach_ma import FrankaReachMA
 from .anymal import Anymal
 from .humanoid_amp import HumanoidAMP
+from .quadcopter import Quadcopter
 
 isaacgym_task_map = {
     "Ant": Ant,
@@ -15,4 +16,5 @@ isaacgym_task_map = {
     "FrankaReachMA": FrankaReachMA,
     "Anymal": Anymal,
     "HumanoidAMP": HumanoidAMP,
+    "Quadcopter": Quadcopter,
 }

@@ -60,6 +60,7 @@ def _load_model(env) -> M.ModelSpec:
 class Anymal(VecTask):
     task_name = "Anymal"
     supports_host_pipeline = False
+    steps_through_simulate = True   # gym.simulate is mg_sim_simulate: link forces (apply_rigid_body_force_tensors)
     acquires_dof_force = True   # anymal.py:113
 
     def __init__(self, cfg, rl_device, sim_device, graphics_device_id, headless, virtual_screen_capture=False,

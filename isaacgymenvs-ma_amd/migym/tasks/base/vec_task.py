@@ -313,6 +313,37 @@ class VecTask(DomainRandomizationMixin, Env):
         """gym.refresh_net_contact_force_tensor (franka_reach_MA.py:563): a no-op -- the bound tensor is written by
         the step itself"""
 
+    # whether the task's step runs gym.simulate as mg_sim_simulate launches of its own (Anymal, HumanoidAMP,
+    # FrankaReachMA): only there can link forces be applied (apply_rigid_body_force_tensors)
+    steps_through_simulate = False
+
+    def apply_rigid_body_force_tensors(self, forces: torch.Tensor, torques=None, space: int = _abi.MG_ENV_SPACE):
+        """gym.apply_rigid_body_force_tensors(sim, forces, torques, space) on articulation links: ``forces`` is the
+        caller's (N, nB, 3) fp32 device tensor in the rigid-body layout (any shape of N*A*nB rows), bound zero-copy and
+        applied at each body's centre of mass in every substep of every later ``simulate`` (mg_sim_set_link_forces),
+        in ``migym.ENV_SPACE`` or ``migym.LOCAL_SPACE`` (the body's own frame, followed substep by substep).  The sim
+        reads the tensor at every simulate and never clears it: write zeros to stop pushing (gym clears applied
+        forces after each simulate).  Torques are not built, and the tasks that step through the fused
+        kernel (Ant, Humanoid, MAAnt, Cartpole, ShadowHand) raise."""
+        if torques is not None:
+            raise NotImplementedError("apply_rigid_body_force_tensors: torques are not built (every use in the "
+                                      "reference's tasks in scope passes None)")
+        if not self.steps_through_simulate:
+            raise NotImplementedError(f"{self.task_name}: link forces are not built for the fused step kernel "
+                                      "(mg_env_step) this task runs; they are applied by mg_sim_simulate, which the "
+                                      "three-launch tasks (Anymal, HumanoidAMP, FrankaReachMA) step through")
+        if space not in (_abi.MG_ENV_SPACE, _abi.MG_LOCAL_SPACE):
+            raise ValueError("apply_rigid_body_force_tensors: space must be ENV_SPACE or LOCAL_SPACE")
+        rows = self.num_actors * len(self.model_spec.bodies)
+        if not (isinstance(forces, torch.Tensor) and forces.dtype == torch.float32 and forces.is_contiguous()
+                and forces.device == torch.device(self.device) and forces.numel() == 3 * rows):
+            raise ValueError(f"apply_rigid_body_force_tensors: forces must be a contiguous fp32 tensor of {rows} rows "
+                             f"of 3 on {self.device} (it is bound, not copied)")
+        self.rb_forces = forces   # alive while the sim reads it
+        self._views.rb_forces, self._views.rb_force_space = forces.data_ptr(), int(space)
+        _abi.check(self._lib.mg_sim_bind(self.sim, _abi.C.byref(self._views)), self._lib)
+        _abi.check(self._lib.mg_sim_set_link_forces(self.sim, 1), self._lib)
+
     def _dynamics(self):
         """the task's DynamicsTensors (migym/dynamics.py); free-base tasks raise NotImplementedError with the
         library's message (mg_dynamics_bind)"""

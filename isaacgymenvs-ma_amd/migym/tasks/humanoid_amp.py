@@ -85,6 +85,7 @@ def _motion_path(env) -> str:
 class HumanoidAMP(VecTask):
     task_name = "HumanoidAMP"
     supports_host_pipeline = False
+    steps_through_simulate = True   # gym.simulate is mg_sim_simulate: link forces (apply_rigid_body_force_tensors)
     acquires_dof_force = True   # humanoid_amp_base.py:88-89
 
     def __init__(self, cfg, rl_device, sim_device, graphics_device_id, headless, virtual_screen_capture=False,
