@@ -24,6 +24,7 @@
 #include "../../include/migym.h"
 #include "device_math.hpp"
 #include "task.hpp"
+#include "task_rows.hpp"
 
 namespace mgh {
 
@@ -271,11 +272,8 @@ __global__ __launch_bounds__(64) void k_amp_post(mg_amp_params ap, mg_amp_views 
     const long long terminated = (ap.enable_early_termination && has_fallen) ? 1 : 0;
     const bool time_out = progress >= (long long)ap.max_episode_length - 1;
     const long long reset = time_out ? 1 : terminated;
-    tb.rew[e] = 1.0f;
-    tb.reset[e] = reset;
+    mgt::tail_store(tb, e, 1.0f, reset, progress, time_out);
     v.terminate[e] = terminated;
-    tb.progress[e] = progress;
-    tb.timeout[e] = (uint8_t)(time_out && reset != 0);
     s_rew[g] = 1.0f;
     s_rst[g] = (float)reset;
   }
@@ -292,20 +290,7 @@ __global__ __launch_bounds__(64) void k_amp_post(mg_amp_params ap, mg_amp_views 
   // the block's rows are one contiguous range of the output tensors
   const int first_env = blockIdx.x * kEnvs;
   const int rows = n_envs - first_env < kEnvs ? n_envs - first_env : kEnvs;
-  const size_t row0 = (size_t)first_env;
-  for (int i = lane; i < rows * kObs; i += 64) {
-    const float x = s_obs[i];
-    tb.obs[row0 * kObs + i] = x;
-    if (tb.obs_clamped) tb.obs_clamped[row0 * kObs + i] = mg::clampf(x, ap.clip_obs);
-  }
-  if (tb.out_pack) {   // the gather's message rows [clamped obs | rew | reset]
-    constexpr int w = kObs + 2;
-    for (int i = lane; i < rows * w; i += 64) {
-      const int r = i / w, c = i - r * w;
-      const float x = c < kObs ? mg::clampf(s_obs[r * kObs + c], ap.clip_obs) : (c == kObs ? s_rew[r] : s_rst[r]);
-      tb.out_pack[row0 * w + i] = x;
-    }
-  }
+  mgt::block_tail(tb, s_obs, s_rew, s_rst, (size_t)first_env, rows, kObs, ap.clip_obs);
 }
 
 // the motion a [motion | phase] pair of uniforms selects: the first index whose cumulative weight exceeds u

@@ -18,6 +18,7 @@
 #include "../../include/migym.h"
 #include "device_math.hpp"
 #include "task.hpp"
+#include "task_rows.hpp"
 
 namespace mga {
 
@@ -39,12 +40,8 @@ struct AnymalState {
 
 // draw `col` of env e's row of the (N, 27) noise layout [positions_offset 12 | velocities 12 | cmd x | y | yaw]
 __device__ __forceinline__ float anymal_uniform(const mg_task_buffers& tb, int e, int col) {
-  return tb.noise ? tb.noise[(size_t)MG_ANYMAL_NOISE_COLS * e + col]
-                  : mg::uniform01(tb.seed, (uint64_t)(tb.env_offset + e), tb.step_counter, (uint32_t)col);
+  return mgt::noise_draw(tb, e, col, MG_ANYMAL_NOISE_COLS);
 }
-
-// torch_rand_float(lower, upper): (upper - lower) * u + lower, the span a Python float
-__device__ __forceinline__ float anymal_rand(float span, float lo, float u) { return span * u + lo; }
 
 // lane `tl` of env e's team applies its share of reset_idx (anymal.py:283-303): DOF tl's position and velocity, command
 // tl - 12, the root row (lane 15).  pos / vel / cmd return what the lane wrote.
@@ -52,14 +49,14 @@ __device__ __forceinline__ void anymal_reset_lane(const mg_anymal_params& ap, co
                                                   const mg_task_buffers& tb, const AnymalState& st, int e, int tl,
                                                   float& pos, float& vel, float& cmd) {
   if (tl < kDofs) {
-    pos = ap.default_dof_pos[tl] * anymal_rand((float)(1.5 - 0.5), 0.5f, anymal_uniform(tb, e, tl));
-    vel = anymal_rand((float)(0.1 - -0.1), -0.1f, anymal_uniform(tb, e, kDofs + tl));
+    pos = ap.default_dof_pos[tl] * mgt::rand_float((float)(1.5 - 0.5), 0.5f, anymal_uniform(tb, e, tl));
+    vel = mgt::rand_float((float)(0.1 - -0.1), -0.1f, anymal_uniform(tb, e, kDofs + tl));
     float* d = st.dof_state + (size_t)2 * ((size_t)kDofs * e + tl);
     d[0] = pos;
     d[1] = vel;
   } else if (tl < kDofs + 3) {
     const int c = tl - kDofs;
-    cmd = anymal_rand(ap.command_span[c], ap.command_lo[c], anymal_uniform(tb, e, 2 * kDofs + c));
+    cmd = mgt::rand_float(ap.command_span[c], ap.command_lo[c], anymal_uniform(tb, e, 2 * kDofs + c));
     v.commands[(size_t)3 * e + c] = cmd;
   } else {
     float* r = st.root_states + (size_t)13 * e;
@@ -170,10 +167,7 @@ __global__ __launch_bounds__(64) void k_anymal_post(mg_anymal_params ap, mg_anym
     const float base = sqrtf(bf[0] * bf[0] + bf[1] * bf[1] + bf[2] * bf[2]);
     const bool time_out = progress >= (long long)ap.max_episode_length - 1;
     const long long reset = (base > 1.0f || knee > 1.0f || time_out) ? 1 : 0;
-    tb.rew[e] = rew;
-    tb.reset[e] = reset;
-    tb.progress[e] = progress;
-    tb.timeout[e] = (uint8_t)(time_out && reset != 0);
+    mgt::tail_store(tb, e, rew, reset, progress, time_out);
     s_rew[g] = rew;
     s_rst[g] = (float)reset;
   }
@@ -181,20 +175,7 @@ __global__ __launch_bounds__(64) void k_anymal_post(mg_anymal_params ap, mg_anym
   // 4. the block's rows are one contiguous range of the output tensors
   const int first_env = blockIdx.x * kEnvs;
   const int rows = n_envs - first_env < kEnvs ? n_envs - first_env : kEnvs;
-  const size_t row0 = (size_t)first_env;
-  for (int i = lane; i < rows * kObs; i += 64) {
-    const float x = s_obs[i];
-    tb.obs[row0 * kObs + i] = x;
-    if (tb.obs_clamped) tb.obs_clamped[row0 * kObs + i] = mg::clampf(x, ap.clip_obs);
-  }
-  if (tb.out_pack) {   // the gather's message rows [clamped obs | rew | reset]
-    constexpr int w = kObs + 2;
-    for (int i = lane; i < rows * w; i += 64) {
-      const int r = i / w, c = i - r * w;
-      const float x = c < kObs ? mg::clampf(s_obs[r * kObs + c], ap.clip_obs) : (c == kObs ? s_rew[r] : s_rst[r]);
-      tb.out_pack[row0 * w + i] = x;
-    }
-  }
+  mgt::block_tail(tb, s_obs, s_rew, s_rst, (size_t)first_env, rows, kObs, ap.clip_obs);
 }
 
 // reset_idx(env_ids): one 16-lane team per listed id.  Off the hot path (the constructor, reset_done).

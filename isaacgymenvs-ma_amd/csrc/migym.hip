@@ -1186,6 +1186,13 @@ int mg_env_step(mg_sim* sim, const mg_task_params* tp, const mg_task_buffers* tb
   return env_step(sim, tp, tb, nullptr, stream);
 }
 
+// the manual-reset copy of the task buffers: reset_idx draws from a stream of the counter RNG that no step uses
+static mg_task_buffers manual_reset_buffers(const mg_task_buffers* tb) {
+  mg_task_buffers t = *tb;
+  t.step_counter = tb->step_counter | (1ull << 62);
+  return t;
+}
+
 int mg_reset_idx(mg_sim* sim, const mg_task_params* tp, const mg_task_buffers* tb, const int32_t* ids, int32_t n,
                  void* stream) {
   if (!sim || !sim->bound || !tp || !tb || n < 0 || (n > 0 && !ids) || !tb->reset || !tb->progress)
@@ -1199,8 +1206,7 @@ int mg_reset_idx(mg_sim* sim, const mg_task_params* tp, const mg_task_buffers* t
     return fail(MG_EINVAL, "mg_reset_idx: locomotion task needs potential buffers");
   }
   if (tp->num_agents > MG_MAX_AGENTS) return fail(MG_EINVAL, "mg_reset_idx: num_agents > MG_MAX_AGENTS");
-  mg_task_buffers t = *tb;
-  t.step_counter = tb->step_counter | (1ull << 62);  // the manual-reset stream of the counter RNG
+  const mg_task_buffers t = manual_reset_buffers(tb);
   hipLaunchKernelGGL(k_reset_idx, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, *tp, sim->views, t, ids,
                      n, sim->n);
   return check_launch("mg_reset_idx");
@@ -1236,6 +1242,22 @@ static int dynamics_sim_ok(const mg_sim* sim, const char* who, bool need_bound) 
   if (!sim->d_dyn) return fail(MG_EINVAL, std::string(who) + ": the model has no DOFs or a body outside its nodes");
   if (need_bound && !sim->bound) return fail(MG_EINVAL, std::string(who) + ": sim not bound");
   return MG_OK;
+}
+
+// the checks the entry points of the three-launch tasks share: every argument given and the sim bound ...
+static int task_args_ok(const mg_sim* sim, const void* params, const void* views, const mg_task_buffers* tb,
+                        const char* who) {
+  if (!sim || !params || !views || !tb) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
+  if (!sim->bound) return fail(MG_EINVAL, std::string(who) + ": sim not bound");
+  return MG_OK;
+}
+// ... the buffers the VecTask.step tail of a *_post launch writes ...
+static bool step_tail_bound(const mg_task_buffers* tb) {
+  return tb->obs && tb->rew && tb->reset && tb->progress && tb->timeout;
+}
+// ... and the state views a *_post launch reads: the injected ones, or the sim's bound ones
+static const mg_state_views& state_views(const mg_sim* sim, const mg_state_views* state) {
+  return state ? *state : sim->views;
 }
 
 int mg_dynamics_bind(mg_sim* sim, const mg_dynamics_views* views) {
@@ -1309,7 +1331,7 @@ size_t mg_reach_views_sizeof(void) { return sizeof(mg_reach_views); }
 static int reach_args_ok(const mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* v,
                          const mg_task_buffers* tb, const char* who) {
   if (int rc = dynamics_sim_ok(sim, who, true)) return rc;
-  if (!rp || !v || !tb) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
+  if (int rc = task_args_ok(sim, rp, v, tb, who)) return rc;
   const int A = rp->num_agents, T = rp->num_targets;
   if (A < 1 || A > MG_MAX_AGENTS || T < 1 || T > A)
     return fail(MG_EINVAL, std::string(who) + ": num_agents must be 1..8 and num_targets 1..num_agents");
@@ -1371,9 +1393,9 @@ int mg_reach_pre(mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* v
 int mg_reach_post(mg_sim* sim, const mg_reach_params* rp, const mg_reach_views* views, const mg_task_buffers* tb,
                   const mg_state_views* state, void* stream) {
   if (int rc = reach_args_ok(sim, rp, views, tb, "mg_reach_post")) return rc;
-  if (!tb->actions || !tb->obs || !tb->rew || !tb->reset || !tb->progress || !tb->timeout)
+  if (!tb->actions || !step_tail_bound(tb))
     return fail(MG_EINVAL, "mg_reach_post: needs actions, obs, rew, reset, progress and timeout");
-  const mg_state_views& s = state ? *state : sim->views;
+  const mg_state_views& s = state_views(sim, state);
   if (!s.dof_state || !s.rigid_body_states || !s.net_contact_forces)
     return fail(MG_EINVAL, "mg_reach_post: needs dof_state, rigid_body_states and net_contact_forces");
   const int n_envs = sim->n / rp->num_agents;
@@ -1391,8 +1413,7 @@ int mg_reach_reset_idx(mg_sim* sim, const mg_reach_params* rp, const mg_reach_vi
     return fail(MG_EINVAL, "mg_reach_reset_idx: bad arguments");
   const int n_envs = sim->n / rp->num_agents;
   if (n == 0 || n_envs == 0) return MG_OK;
-  mg_task_buffers t = *tb;
-  t.step_counter = tb->step_counter | (1ull << 62);   // the manual-reset stream of the counter RNG, as mg_reset_idx
+  const mg_task_buffers t = manual_reset_buffers(tb);
   hipLaunchKernelGGL(mgr::k_reach_reset_idx, dim3((n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, *rp,
                      *views, t, sim->views.dof_state, ids, n, n_envs);
   return check_launch("mg_reach_reset_idx");
@@ -1405,8 +1426,7 @@ size_t mg_anymal_views_sizeof(void) { return sizeof(mg_anymal_views); }
 // the shared argument check: a bound free-base 12-DOF sim whose body count matches the task constants
 static int anymal_args_ok(const mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* v,
                           const mg_task_buffers* tb, const char* who) {
-  if (!sim || !ap || !v || !tb) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
-  if (!sim->bound) return fail(MG_EINVAL, std::string(who) + ": sim not bound");
+  if (int rc = task_args_ok(sim, ap, v, tb, who)) return rc;
   const mg_model& m = sim->host_model;
   if (m.fixed_base || m.obj_type || m.num_nodes - 1 != MG_ANYMAL_DOFS)
     return fail(MG_EINVAL, std::string(who) + ": needs a free-base model of 12 DOFs without a free object");
@@ -1436,9 +1456,9 @@ int mg_anymal_pre(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views
 int mg_anymal_post(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal_views* views, const mg_task_buffers* tb,
                    const mg_state_views* state, void* stream) {
   if (int rc = anymal_args_ok(sim, ap, views, tb, "mg_anymal_post")) return rc;
-  if (!tb->actions || !tb->obs || !tb->rew || !tb->reset || !tb->progress || !tb->timeout)
+  if (!tb->actions || !step_tail_bound(tb))
     return fail(MG_EINVAL, "mg_anymal_post: needs actions, obs, rew, reset, progress and timeout");
-  const mg_state_views& s = state ? *state : sim->views;
+  const mg_state_views& s = state_views(sim, state);
   if (!s.root_states || !s.dof_state || !s.dof_force || !s.net_contact_forces)
     return fail(MG_EINVAL, "mg_anymal_post: needs root_states, dof_state, dof_force and net_contact_forces");
   if (sim->n == 0) return MG_OK;
@@ -1454,8 +1474,7 @@ int mg_anymal_reset_idx(mg_sim* sim, const mg_anymal_params* ap, const mg_anymal
   if (n < 0 || (n > 0 && !ids) || !tb->reset || !tb->progress || !sim->views.root_states || !sim->views.dof_state)
     return fail(MG_EINVAL, "mg_anymal_reset_idx: bad arguments");
   if (n == 0 || sim->n == 0) return MG_OK;
-  mg_task_buffers t = *tb;
-  t.step_counter = tb->step_counter | (1ull << 62);   // the manual-reset stream of the counter RNG, as mg_reset_idx
+  const mg_task_buffers t = manual_reset_buffers(tb);
   mga::AnymalState st{sim->views.root_states, sim->views.dof_state, sim->views.dof_force,
                       sim->views.net_contact_forces};
   hipLaunchKernelGGL(mga::k_anymal_reset_idx, dim3((n + mga::kEnvs - 1) / mga::kEnvs), dim3(64), 0,
@@ -1470,8 +1489,7 @@ size_t mg_quadcopter_views_sizeof(void) { return sizeof(mg_quadcopter_views); }
 // the shared argument check: a bound free-base sim of 8 DOFs and 9 bodies, the rotor rows inside the force tensor
 static int quadcopter_args_ok(const mg_sim* sim, const mg_quadcopter_params* qp, const mg_quadcopter_views* v,
                               const mg_task_buffers* tb, const char* who) {
-  if (!sim || !qp || !v || !tb) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
-  if (!sim->bound) return fail(MG_EINVAL, std::string(who) + ": sim not bound");
+  if (int rc = task_args_ok(sim, qp, v, tb, who)) return rc;
   const mg_model& m = sim->host_model;
   if (m.fixed_base || m.obj_type || m.num_nodes - 1 != MG_QUAD_DOFS || m.num_bodies != MG_QUAD_BODIES)
     return fail(MG_EINVAL, std::string(who) + ": needs a free-base model of 8 DOFs and 9 bodies without a free object");
@@ -1501,9 +1519,9 @@ int mg_quadcopter_pre(mg_sim* sim, const mg_quadcopter_params* qp, const mg_quad
 int mg_quadcopter_post(mg_sim* sim, const mg_quadcopter_params* qp, const mg_quadcopter_views* views,
                        const mg_task_buffers* tb, const mg_state_views* state, void* stream) {
   if (int rc = quadcopter_args_ok(sim, qp, views, tb, "mg_quadcopter_post")) return rc;
-  if (!tb->obs || !tb->rew || !tb->reset || !tb->progress || !tb->timeout)
+  if (!step_tail_bound(tb))
     return fail(MG_EINVAL, "mg_quadcopter_post: needs obs, rew, reset, progress and timeout");
-  const mg_state_views& s = state ? *state : sim->views;
+  const mg_state_views& s = state_views(sim, state);
   if (!s.root_states || !s.dof_state) return fail(MG_EINVAL, "mg_quadcopter_post: needs root_states and dof_state");
   if (sim->n == 0) return MG_OK;
   hipLaunchKernelGGL(mgq::k_quad_post, dim3((sim->n + mgq::kEnvs - 1) / mgq::kEnvs), dim3(64), 0, (hipStream_t)stream,
@@ -1517,8 +1535,7 @@ int mg_quadcopter_reset_idx(mg_sim* sim, const mg_quadcopter_params* qp, const m
   if (n < 0 || (n > 0 && !ids) || !tb->reset || !tb->progress)
     return fail(MG_EINVAL, "mg_quadcopter_reset_idx: bad arguments");
   if (n == 0 || sim->n == 0) return MG_OK;
-  mg_task_buffers t = *tb;
-  t.step_counter = tb->step_counter | (1ull << 62);   // the manual-reset stream of the counter RNG, as mg_reset_idx
+  const mg_task_buffers t = manual_reset_buffers(tb);
   hipLaunchKernelGGL(mgq::k_quad_reset_idx, dim3((n + mgq::kEnvs - 1) / mgq::kEnvs), dim3(64), 0, (hipStream_t)stream,
                      *qp, t, sim->views.root_states, sim->views.dof_state, ids, n, sim->n);
   return check_launch("mg_quadcopter_reset_idx");
@@ -1648,9 +1665,8 @@ static int amp_motions_ok(const mg_amp_views* v, const char* who) {
 // a bound free-base 28-DOF, 15-body sim
 static int amp_args_ok(const mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* v, const mg_task_buffers* tb,
                        const char* who) {
-  if (!sim || !tb) return fail(MG_EINVAL, std::string(who) + ": bad arguments");
+  if (int rc = task_args_ok(sim, ap, v, tb, who)) return rc;
   if (int rc = amp_params_ok(ap, v, who)) return rc;
-  if (!sim->bound) return fail(MG_EINVAL, std::string(who) + ": sim not bound");
   const mg_model& m = sim->host_model;
   if (m.fixed_base || m.obj_type || m.num_nodes - 1 != MG_AMP_DOFS || m.num_bodies != MG_AMP_BODIES)
     return fail(MG_EINVAL, std::string(who) + ": needs a free-base model of 28 DOFs and 15 bodies without a free object");
@@ -1677,9 +1693,9 @@ int mg_amp_pre(mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* views, 
 int mg_amp_post(mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* views, const mg_task_buffers* tb,
                 const mg_state_views* state, void* stream) {
   if (int rc = amp_args_ok(sim, ap, views, tb, "mg_amp_post")) return rc;
-  if (!tb->obs || !tb->rew || !tb->reset || !tb->progress || !tb->timeout || !views->amp_obs || !views->terminate)
+  if (!step_tail_bound(tb) || !views->amp_obs || !views->terminate)
     return fail(MG_EINVAL, "mg_amp_post: needs obs, rew, reset, progress, timeout, amp_obs and terminate");
-  const mg_state_views& s = state ? *state : sim->views;
+  const mg_state_views& s = state_views(sim, state);
   if (!s.root_states || !s.dof_state || !s.rigid_body_states || !s.net_contact_forces)
     return fail(MG_EINVAL, "mg_amp_post: needs root_states, dof_state, rigid_body_states and net_contact_forces");
   if (sim->n == 0) return MG_OK;
@@ -1698,8 +1714,7 @@ int mg_amp_reset_idx(mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* v
   if (ap->state_init != MG_AMP_INIT_DEFAULT)
     if (int rc = amp_motions_ok(views, "mg_amp_reset_idx")) return rc;
   if (n == 0 || sim->n == 0) return MG_OK;
-  mg_task_buffers t = *tb;
-  t.step_counter = tb->step_counter | (1ull << 62);   // the manual-reset stream of the counter RNG, as mg_reset_idx
+  const mg_task_buffers t = manual_reset_buffers(tb);
   mgh::AmpState st{sim->views.root_states, sim->views.dof_state, sim->views.rigid_body_states,
                    sim->views.net_contact_forces};
   hipLaunchKernelGGL(mgh::k_amp_reset_idx, dim3((n + mgh::kEnvs - 1) / mgh::kEnvs), dim3(64), 0, (hipStream_t)stream,

@@ -18,21 +18,23 @@
 #include "../../include/migym.h"
 #include "device_math.hpp"
 #include "task.hpp"
+#include "task_rows.hpp"
 
 namespace mgq {
 
-constexpr int kEnvs = 64;   // envs per block
+constexpr int kEnvs = mgt::kLanes;   // envs per block: one per lane
 constexpr int kDofs = MG_QUAD_DOFS, kObs = MG_QUAD_OBS, kActs = MG_QUAD_ACTIONS, kFrc = 3 * MG_QUAD_BODIES;
 
 #pragma clang fp contract(off)
 
+using mgt::rand_float;
+using mgt::rows_load;
+using mgt::rows_store;
+
 // draw `col` of env e's row of the (N, 11) noise layout [x | y | z | dof position 8]
 __device__ __forceinline__ float quad_uniform(const mg_task_buffers& tb, int e, int col) {
-  return tb.noise ? tb.noise[(size_t)MG_QUAD_NOISE_COLS * e + col]
-                  : mg::uniform01(tb.seed, (uint64_t)(tb.env_offset + e), tb.step_counter, (uint32_t)col);
+  return mgt::noise_draw(tb, e, col, MG_QUAD_NOISE_COLS);
 }
-// torch_rand_float(lower, upper): (upper - lower) * u + lower, the span a Python float
-__device__ __forceinline__ float quad_rand(float span, float lo, float u) { return span * u + lo; }
 
 // reset_idx of env e (quadcopter.py:284-299): DOF state and root row written, reset and progress cleared; pos returns
 // the new DOF positions
@@ -42,28 +44,20 @@ __device__ __forceinline__ void quad_reset_env(const mg_quadcopter_params& qp, c
   float row[13];
 #pragma unroll
   for (int c = 0; c < 13; c++) row[c] = qp.init_root[c];
-  row[0] = row[0] + quad_rand((float)(1.5 - -1.5), -1.5f, quad_uniform(tb, e, 0));
-  row[1] = row[1] + quad_rand((float)(1.5 - -1.5), -1.5f, quad_uniform(tb, e, 1));
-  row[2] = row[2] + quad_rand((float)(1.5 - -0.2), -0.2f, quad_uniform(tb, e, 2));
+  row[0] = row[0] + rand_float((float)(1.5 - -1.5), -1.5f, quad_uniform(tb, e, 0));
+  row[1] = row[1] + rand_float((float)(1.5 - -1.5), -1.5f, quad_uniform(tb, e, 1));
+  row[2] = row[2] + rand_float((float)(1.5 - -0.2), -0.2f, quad_uniform(tb, e, 2));
 #pragma unroll
   for (int c = 0; c < 13; c++) r[c] = row[c];
   float* d = dof_state + (size_t)2 * kDofs * e;
 #pragma unroll
   for (int j = 0; j < kDofs; j++) {
-    pos[j] = quad_rand((float)(0.2 - -0.2), -0.2f, quad_uniform(tb, e, 3 + j));
+    pos[j] = rand_float((float)(0.2 - -0.2), -0.2f, quad_uniform(tb, e, 3 + j));
     d[2 * j] = pos[j];
     d[2 * j + 1] = 0.0f;
   }
   tb.reset[e] = 0;
   tb.progress[e] = 0;
-}
-
-// the block's `rows` rows of `w` floats of a tensor, between memory and LDS, over consecutive addresses
-__device__ __forceinline__ void rows_load(float* s, const float* g, int rows, int w) {
-  for (int i = threadIdx.x; i < rows * w; i += kEnvs) s[i] = g[i];
-}
-__device__ __forceinline__ void rows_store(float* g, const float* s, int rows, int w) {
-  for (int i = threadIdx.x; i < rows * w; i += kEnvs) g[i] = s[i];
 }
 
 // pre_physics_step
@@ -129,8 +123,8 @@ __global__ __launch_bounds__(64) void k_quad_post(mg_quadcopter_params qp, mg_ta
   __shared__ float s_rst[kEnvs];
   const int first = blockIdx.x * kEnvs, l = threadIdx.x, e = first + l;
   const int rows = n_envs - first < kEnvs ? n_envs - first : kEnvs;
-  for (int i = l; i < rows * 13; i += kEnvs) s_root[i] = root_states[(size_t)first * 13 + i];
-  for (int i = l; i < rows * 2 * kDofs; i += kEnvs) s_dof[i] = dof_state[(size_t)first * 2 * kDofs + i];
+  rows_load(s_root, root_states + (size_t)first * 13, rows, 13);
+  rows_load(s_dof, dof_state + (size_t)first * 2 * kDofs, rows, 2 * kDofs);
   __syncthreads();
   if (l < rows) {
     const long long progress = (long long)tb.progress[e] + 1;
@@ -163,28 +157,12 @@ __global__ __launch_bounds__(64) void k_quad_post(mg_quadcopter_params qp, mg_ta
     const bool die = dist > 3.0f || r[2] < 0.3f;
     const bool time_out = progress >= (long long)qp.max_episode_length - 1;
     const long long reset = (time_out || die) ? 1 : 0;
-    tb.rew[e] = rew;
-    tb.reset[e] = reset;
-    tb.progress[e] = progress;
-    tb.timeout[e] = (uint8_t)(time_out && reset != 0);
+    mgt::tail_store(tb, e, rew, reset, progress, time_out);
     s_rew[l] = rew;
     s_rst[l] = (float)reset;
   }
   __syncthreads();
-  const size_t row0 = (size_t)first;
-  for (int i = l; i < rows * kObs; i += kEnvs) {
-    const float x = s_obs[i];
-    tb.obs[row0 * kObs + i] = x;
-    if (tb.obs_clamped) tb.obs_clamped[row0 * kObs + i] = mg::clampf(x, qp.clip_obs);
-  }
-  if (tb.out_pack) {   // the gather's message rows [clamped obs | rew | reset]
-    constexpr int w = kObs + 2;
-    for (int i = l; i < rows * w; i += kEnvs) {
-      const int rr = i / w, c = i - rr * w;
-      const float x = c < kObs ? mg::clampf(s_obs[rr * kObs + c], qp.clip_obs) : (c == kObs ? s_rew[rr] : s_rst[rr]);
-      tb.out_pack[row0 * w + i] = x;
-    }
-  }
+  mgt::block_tail(tb, s_obs, s_rew, s_rst, (size_t)first, rows, kObs, qp.clip_obs);
 }
 
 // reset_idx(env_ids): one lane per listed id.  Off the hot path (reset_done).

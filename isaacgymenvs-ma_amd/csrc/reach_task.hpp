@@ -19,6 +19,7 @@
 #include "device_math.hpp"
 #include "dynamics_tensors.hpp"
 #include "task.hpp"
+#include "task_rows.hpp"
 
 namespace mgr {
 
@@ -39,9 +40,7 @@ struct ReachState {
 
 // draw `col` of env e's row of the (N, 3 T + 9) noise layout [z (T) | xy (2 T) | DOF (9)]
 __device__ __forceinline__ float reach_uniform(const mg_reach_params& rp, const mg_task_buffers& tb, int e, int col) {
-  const int width = 3 * rp.num_targets + kReachDofs;
-  return tb.noise ? tb.noise[(size_t)width * e + col]
-                  : mg::uniform01(tb.seed, (uint64_t)(tb.env_offset + e), tb.step_counter, (uint32_t)col);
+  return mgt::noise_draw(tb, e, col, 3 * rp.num_targets + kReachDofs);
 }
 
 // _reset_init_cube_state + the copy into _cubeA_state for cube t of env e; pos = the new position
@@ -183,33 +182,15 @@ __global__ __launch_bounds__(64) void k_reach_post(mg_reach_params rp, mg_reach_
     const float max_ep_m1 = (float)rp.max_episode_length - 1.0f;
     if ((float)progress >= max_ep_m1) reset = 1;
     // 6. the VecTask.step tail
-    tb.rew[a] = rew;
-    tb.reset[a] = reset;
-    tb.progress[a] = progress;
-    tb.timeout[a] = (uint8_t)(((float)progress >= max_ep_m1) && (reset != 0));
+    mgt::tail_store(tb, a, rew, reset, progress, (float)progress >= max_ep_m1);
+    s_rew[g * A + k] = rew;   // by packed row, as s_obs
+    s_rst[g * A + k] = (float)reset;
   }
-  s_rew[lane] = rew;
-  s_rst[lane] = (float)reset;
   __syncthreads();
   // the block's rows are one contiguous range of the output tensors
   const int first_env = blockIdx.x * kEnvs;
   const int envs_here = n_envs - first_env < kEnvs ? n_envs - first_env : kEnvs;
-  const int rows = envs_here * A;
-  const size_t row0 = (size_t)first_env * A;
-  for (int i = lane; i < rows * no; i += 64) {
-    const float x = s_obs[i];
-    tb.obs[row0 * no + i] = x;
-    if (tb.obs_clamped) tb.obs_clamped[row0 * no + i] = mg::clampf(x, rp.clip_obs);
-  }
-  if (tb.out_pack) {   // the gather's message rows [clamped obs | rew | reset]
-    const int w = no + 2;
-    for (int i = lane; i < rows * w; i += 64) {
-      const int r = i / w, c = i - r * w;
-      const int src = (r / A) * kGroup + (r % A);   // the lane that holds row r's reward and reset
-      const float x = c < no ? mg::clampf(s_obs[r * no + c], rp.clip_obs) : (c == no ? s_rew[src] : s_rst[src]);
-      tb.out_pack[row0 * w + i] = x;
-    }
-  }
+  mgt::block_tail(tb, s_obs, s_rew, s_rst, (size_t)first_env * A, envs_here * A, no, rp.clip_obs);
 }
 
 // reset_idx(agent_ids): each block counts, in LDS, the ids that fall into its 256 envs (bincount(ids // A)), then one

@@ -18,7 +18,6 @@ What differs from the reference:
 """
 from __future__ import annotations
 
-import math
 import os
 
 import numpy as np
@@ -27,7 +26,7 @@ import torch
 from .. import _abi
 from .. import model as M
 from .. import taskdefs
-from .base.vec_task import VecTask
+from .base.simulate_task import SimulateTask, state_tensors
 
 _TASKS_DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -57,18 +56,20 @@ def _load_model(env) -> M.ModelSpec:
         "env.asset.assetRoot / assetFileName to the URDF")
 
 
-class Anymal(VecTask):
+class Anymal(SimulateTask):
+    """``reset_idx(env_ids)`` (anymal.py:278-304): the listed envs get ``dof_pos = default * U(0.5, 1.5)``, ``dof_vel =
+    U(-0.1, 0.1)``, the base init state, three new commands and ``progress = 0``; like the reference's, it leaves
+    ``reset_buf`` of those envs at 1 (the next step's compute_reward overwrites it).  ``set_reset_noise``: per-env
+    U(0,1) rows (N, 27) = [positions_offset 12 | velocities 12 | command x | y | yaw], the reference's draw order
+    (anymal.py:283-301)."""
     task_name = "Anymal"
-    supports_host_pipeline = False
-    steps_through_simulate = True   # gym.simulate is mg_sim_simulate: link forces (apply_rigid_body_force_tensors)
+    entry = "mg_anymal"
     acquires_dof_force = True   # anymal.py:113
 
     def __init__(self, cfg, rl_device, sim_device, graphics_device_id, headless, virtual_screen_capture=False,
                  force_render=False):
+        self._refuse_randomize(cfg)
         env = cfg["env"]
-        if bool((cfg.get("task", {}) or {}).get("randomize", False)):
-            raise NotImplementedError("Anymal: task.randomize is not built for this task (domain randomization runs "
-                                      "inside the fused step kernels, which this task does not use)")
         learn, ctl = env["learn"], env["control"]
         self.lin_vel_scale, self.ang_vel_scale = learn["linearVelocityScale"], learn["angularVelocityScale"]
         self.dof_pos_scale, self.dof_vel_scale = learn["dofPositionScale"], learn["dofVelocityScale"]
@@ -111,12 +112,6 @@ class Anymal(VecTask):
                            "ang_vel_z": learn["angularVelocityZRewardScale"] * dt32,
                            "torque": learn["torqueRewardScale"] * dt32}
         self.sim_params = taskdefs.sim_params(self.cfg, taskdefs.TASK_INFO["Anymal"][5], 1)
-        self._model_np = _abi.model_bytes(spec)
-        torch.cuda.set_device(self.device_id)
-        h = _abi.C.c_void_p()
-        _abi.check(self._lib.mg_sim_create(self._model_np.ctypes.data, _abi.C.byref(self.sim_params), N,
-                                           self.device_id, _abi.C.byref(h)), self._lib)
-        self.sim = h
         dev, f = self.device, torch.float32
         self.dof_names = list(spec.dof_names)
         names = [b.name for b in spec.bodies]
@@ -148,67 +143,10 @@ class Anymal(VecTask):
         v.dof_actuation, v.dof_targets = _abi.ptr(self.dof_actuation), _abi.ptr(self.dof_targets)
         v.dof_force = _abi.ptr(self.dof_force_tensor)
         v.net_contact_forces = _abi.ptr(self.net_contact_force_tensor)
-        self._views = v
-        _abi.check(self._lib.mg_sim_bind(self.sim, _abi.C.byref(v)), self._lib)
+        self._create_sim_handle(spec, v)
         av = _abi.AnymalViews()
         av.commands, av.dof_targets = _abi.ptr(self.commands), _abi.ptr(self.dof_targets)
-        self._anymal_views = av
+        self._bind_task(ap, av, noise_shape=(N, _abi.MG_ANYMAL_NOISE_COLS))
 
-    def allocate_buffers(self):
-        dev, n = self.device, self.num_envs
-        self.obs_buf = torch.zeros((n, self.num_obs), device=dev, dtype=torch.float)
-        self.states_buf = torch.zeros((n, self.num_states), device=dev, dtype=torch.float)
-        self.rew_buf = torch.zeros(n, device=dev, dtype=torch.float)
-        self.reset_buf = torch.ones(n, device=dev, dtype=torch.long)
-        self.timeout_buf = torch.zeros(n, device=dev, dtype=torch.bool)
-        self.progress_buf = torch.zeros(n, device=dev, dtype=torch.long)
-        self.randomize_buf = torch.zeros(n, device=dev, dtype=torch.long)
-        self.actions = torch.zeros((n, self.num_actions), device=dev, dtype=torch.float)
-        self._clamp_obs = math.isfinite(float(self.clip_obs))
-        self.obs_clamped = torch.zeros_like(self.obs_buf) if self._clamp_obs else self.obs_buf
-        self._noise = None
-        tb = _abi.TaskBuffers()
-        tb.actions_out, tb.obs = _abi.ptr(self.actions), _abi.ptr(self.obs_buf)
-        tb.obs_clamped = _abi.ptr(self.obs_clamped) if self._clamp_obs else None
-        tb.rew, tb.reset, tb.progress = _abi.ptr(self.rew_buf), _abi.ptr(self.reset_buf), _abi.ptr(self.progress_buf)
-        tb.timeout = _abi.ptr(self.timeout_buf)
-        tb.seed, tb.env_offset = self.seed, self.env_offset
-        self._tb = tb
-
-    env_state_tensors = tuple(k for k in VecTask.env_state_tensors
-                              if k not in ("sensor_tensor", "potentials", "prev_potentials", "up_vec", "heading_vec",
-                                           "env_props", "randomize_buf_actors")) + (
-        "dof_targets", "net_contact_force_tensor", "commands")
-
-    # ---------------------------------------------------------------------------------- hot path
-    def _launch_step(self, tb, stream):
-        lib, ap, av = self._lib, _abi.C.byref(self.anymal_params), _abi.C.byref(self._anymal_views)
-        _abi.check(lib.mg_anymal_pre(self.sim, ap, av, _abi.C.byref(tb), stream), lib)
-        for _ in range(max(1, self.control_freq_inv)):
-            _abi.check(lib.mg_sim_simulate(self.sim, stream), lib)
-        _abi.check(lib.mg_anymal_post(self.sim, ap, av, _abi.C.byref(tb), None, stream), lib)
-
-    # ---------------------------------------------------------------------------------- API
-    def reset_idx(self, env_ids, goal_env_ids=None):
-        """reset_idx(env_ids) (anymal.py:278-304), one launch (``mg_anymal_reset_idx``): the listed envs get
-        ``dof_pos = default * U(0.5, 1.5)``, ``dof_vel = U(-0.1, 0.1)``, the base init state, three new commands and
-        ``progress = 0``; like the reference's, it leaves ``reset_buf`` of those envs at 1 (the next step's
-        compute_reward overwrites it)."""
-        ids = torch.as_tensor(env_ids, device=self.device).flatten().to(torch.int32).contiguous()
-        if ids.numel() == 0:
-            return
-        self._reset_ids = ids   # alive until the launch has consumed it
-        tb = self._tb
-        tb.step_counter = self.control_steps
-        tb.noise = _abi.ptr(self._noise)
-        _abi.check(self._lib.mg_anymal_reset_idx(self.sim, _abi.C.byref(self.anymal_params),
-                                                 _abi.C.byref(self._anymal_views), _abi.C.byref(tb), ids.data_ptr(),
-                                                 int(ids.numel()), self._stream()), self._lib)
-
-    def set_reset_noise(self, noise):
-        """Inject per-env U(0,1) rows (N, 27) = [positions_offset 12 | velocities 12 | command x | y | yaw], the
-        reference's draw order (anymal.py:283-301), instead of the device RNG."""
-        want = (self.num_envs, _abi.MG_ANYMAL_NOISE_COLS)
-        if noise is not None and tuple(noise.shape) != want:
-            raise ValueError(f"reset noise must be {want}, got {tuple(noise.shape)}")
-        super().set_reset_noise(noise)
+    env_state_tensors = state_tensors(drop=("sensor_tensor",),
+                                      add=("dof_targets", "net_contact_force_tensor", "commands"))

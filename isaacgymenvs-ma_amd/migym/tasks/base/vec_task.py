@@ -151,12 +151,6 @@ class VecTask(DomainRandomizationMixin, Env):
         self.num_actors = self.num_envs * self.num_agents
         self.sim_params = taskdefs.sim_params(self.cfg, max_contacts, self.num_agents)
         self.task_params = taskdefs.task_params(self.task_name, self.cfg, self.model_spec)
-        self._model_np = _abi.model_bytes(self.model_spec)
-        torch.cuda.set_device(self.device_id)
-        h = _abi.C.c_void_p()
-        _abi.check(self._lib.mg_sim_create(self._model_np.ctypes.data, _abi.C.byref(self.sim_params),
-                                           self.num_actors, self.device_id, _abi.C.byref(h)), self._lib)
-        self.sim = h
         dev, f = self.device, torch.float32
         A, nd, ns = self.num_actors, self.num_dof, len(self.model_spec.sensors)
         # gym-visible state tensors (acquire_*_tensor + wrap_tensor): zero-copy, owned by torch
@@ -189,10 +183,23 @@ class VecTask(DomainRandomizationMixin, Env):
         # stays zero
         v.dof_force = _abi.ptr(self.dof_force_tensor) if self.acquires_dof_force else None
         v.rigid_body_states = None
-        self._views = v
-        _abi.check(self._lib.mg_sim_bind(self.sim, _abi.C.byref(v)), self._lib)
+        self._create_sim_handle(self.model_spec, v)
 
-    def allocate_buffers(self):
+    def _create_sim_handle(self, spec, views):
+        """``self.sim``: ``mg_sim_create`` of ``num_actors`` actors of ``spec`` under ``self.sim_params``, with
+        ``views`` (kept as ``self._views``) bound to it"""
+        self._model_np = _abi.model_bytes(spec)
+        torch.cuda.set_device(self.device_id)
+        h = _abi.C.c_void_p()
+        _abi.check(self._lib.mg_sim_create(self._model_np.ctypes.data, _abi.C.byref(self.sim_params),
+                                           self.num_actors, self.device_id, _abi.C.byref(h)), self._lib)
+        self.sim = h
+        self._views = views
+        _abi.check(self._lib.mg_sim_bind(self.sim, _abi.C.byref(views)), self._lib)
+
+    def _allocate_step_buffers(self):
+        """the buffers every task's step writes, and the ``mg_task_buffers`` that names them: one row per actor,
+        ``states_buf`` and ``randomize_buf`` one per env"""
         dev, A = self.device, self.num_actors
         self.obs_buf = torch.zeros((A, self.num_obs), device=dev, dtype=torch.float)
         self.states_buf = torch.zeros((self.num_envs, self.num_states), device=dev, dtype=torch.float)
@@ -204,6 +211,18 @@ class VecTask(DomainRandomizationMixin, Env):
         self.actions = torch.zeros((A, self.num_actions), device=dev, dtype=torch.float)
         self._clamp_obs = math.isfinite(float(self.clip_obs))
         self.obs_clamped = torch.zeros_like(self.obs_buf) if self._clamp_obs else self.obs_buf
+        self._noise = None
+        tb = _abi.TaskBuffers()
+        tb.actions_out, tb.obs = _abi.ptr(self.actions), _abi.ptr(self.obs_buf)
+        tb.obs_clamped = _abi.ptr(self.obs_clamped) if self._clamp_obs else None
+        tb.rew, tb.reset, tb.progress = _abi.ptr(self.rew_buf), _abi.ptr(self.reset_buf), _abi.ptr(self.progress_buf)
+        tb.timeout = _abi.ptr(self.timeout_buf)
+        tb.seed, tb.env_offset = self.seed, self.env_offset
+        self._tb = tb
+
+    def allocate_buffers(self):
+        self._allocate_step_buffers()
+        dev, A, tb = self.device, self.num_actors, self._tb
         pot = -1000.0 / self.dt
         self.potentials = torch.full((A,), pot, device=dev, dtype=torch.float)
         self.prev_potentials = self.potentials.clone()
@@ -216,16 +235,8 @@ class VecTask(DomainRandomizationMixin, Env):
             self.targets += self.root_states[:, 0:3] - self.root_states[:, 0:3].new_tensor(
                 list(self.task_params.start_pos))
             self.targets[:, 2] = 0.0
-        self._noise = None
-        tb = _abi.TaskBuffers()
-        tb.actions_out, tb.obs = _abi.ptr(self.actions), _abi.ptr(self.obs_buf)
-        tb.obs_clamped = _abi.ptr(self.obs_clamped) if self._clamp_obs else None
-        tb.rew, tb.reset, tb.progress = _abi.ptr(self.rew_buf), _abi.ptr(self.reset_buf), _abi.ptr(self.progress_buf)
-        tb.timeout = _abi.ptr(self.timeout_buf)
         tb.potentials, tb.prev_potentials = _abi.ptr(self.potentials), _abi.ptr(self.prev_potentials)
         tb.up_vec, tb.heading_vec = _abi.ptr(self.up_vec), _abi.ptr(self.heading_vec)
-        tb.seed, tb.env_offset = self.seed, self.env_offset
-        self._tb = tb
 
     # ---------------------------------------------------------------------------------- hot path
     def _stream(self):

@@ -29,7 +29,7 @@ import torch
 from .. import _abi
 from .. import model as M
 from .. import taskdefs
-from .base.vec_task import VecTask
+from .base.simulate_task import SimulateTask, state_tensors
 
 _TASKS_DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -57,10 +57,13 @@ def _load_model(env) -> M.ModelSpec:
         "env.asset.assetRoot / assetFileNameFranka to the URDF (kinematics only: its masses are the loader's)")
 
 
-class FrankaReachMA(VecTask):
+class FrankaReachMA(SimulateTask):
+    """``reset_idx(agent_ids)`` (franka_reach_MA.py:616-679): the envs whose agents are all listed (bincount(agent_ids
+    // A) >= A, a repeated id counting twice) get new cubes, DOF state, targets and zero actuation, and their progress
+    / reset cleared; a partial list resets nothing.  ``set_reset_noise``: per-env U(0,1) rows (N, 3 T + 9) = [z of each
+    cube (T) | xy of each cube (2 T) | DOF noise (9)], the reference's draw order (franka_reach_MA.py:692, 696, 631)."""
     task_name = "FrankaReachMA"
-    supports_host_pipeline = False
-    steps_through_simulate = True   # gym.simulate is mg_sim_simulate: link forces (apply_rigid_body_force_tensors)
+    entry = "mg_reach"
 
     def __init__(self, cfg, rl_device, sim_device, graphics_device_id, headless, virtual_screen_capture=False,
                  force_render=False):
@@ -74,9 +77,7 @@ class FrankaReachMA(VecTask):
         if float(env.get("frankaPositionNoise", 0.0)) > 0 or float(env.get("frankaRotationNoise", 0.0)) > 0:
             raise NotImplementedError("frankaPositionNoise / frankaRotationNoise > 0 are not implemented "
                                       "(franka_reach_MA.py:402-407 raises too)")
-        if bool((cfg.get("task", {}) or {}).get("randomize", False)):
-            raise NotImplementedError("FrankaReachMA: task.randomize is not built for this task (domain randomization "
-                                      "runs inside the fused step kernels, which this task does not use)")
+        self._refuse_randomize(cfg)
         A, T = taskdefs.reach_counts(env)
         env["numAgents"] = A
         self.num_targets = T
@@ -109,12 +110,6 @@ class FrankaReachMA(VecTask):
         self.num_actors = n = N * A
         max_contacts = taskdefs.TASK_INFO["FrankaReachMA"][5]
         self.sim_params = taskdefs.sim_params(self.cfg, max_contacts, A)
-        self._model_np = _abi.model_bytes(spec)
-        torch.cuda.set_device(self.device_id)
-        h = _abi.C.c_void_p()
-        _abi.check(self._lib.mg_sim_create(self._model_np.ctypes.data, _abi.C.byref(self.sim_params), n,
-                                           self.device_id, _abi.C.byref(h)), self._lib)
-        self.sim = h
         dev, f = self.device, torch.float32
         # root rows [arm_0 .. arm_{A-1}] per env on the reference's circle (franka_reach_MA.py:414-420)
         pos, rot = taskdefs.franka_start_poses(A)
@@ -161,12 +156,11 @@ class FrankaReachMA(VecTask):
         v.dof_actuation, v.dof_targets = _abi.ptr(self.dof_actuation), _abi.ptr(self.dof_targets)
         v.rigid_body_states = _abi.ptr(self.rigid_body_states)
         v.net_contact_forces = _abi.ptr(self.net_contact_force_tensor)
-        self._views = v
-        _abi.check(self._lib.mg_sim_bind(self.sim, _abi.C.byref(v)), self._lib)
+        self._create_sim_handle(spec, v)
         rv = _abi.ReachViews()
         rv.cube_states, rv.init_cube_states = _abi.ptr(self._cubeA_state), _abi.ptr(self._init_cubeA_state)
         rv.dof_targets, rv.dof_actuation = _abi.ptr(self.dof_targets), _abi.ptr(self.dof_actuation)
-        self._reach_views = rv
+        self._bind_task(rp, rv, noise_shape=(N, 3 * T + 9))
 
     def render_boxes(self):
         """the target cubes, as the renderer's extra boxes"""
@@ -174,40 +168,9 @@ class FrankaReachMA(VecTask):
         half = torch.full((self.num_envs, self.num_targets, 3), h, device=self.device, dtype=torch.float32)
         return torch.cat([self._cubeA_state[..., 0:7], half], dim=-1).contiguous()
 
-    def allocate_buffers(self):
-        dev, n = self.device, self.num_actors
-        self.obs_buf = torch.zeros((n, self.num_obs), device=dev, dtype=torch.float)
-        self.states_buf = torch.zeros((self.num_envs, self.num_states), device=dev, dtype=torch.float)
-        self.rew_buf = torch.zeros(n, device=dev, dtype=torch.float)
-        self.reset_buf = torch.ones(n, device=dev, dtype=torch.long)
-        self.timeout_buf = torch.zeros(n, device=dev, dtype=torch.bool)
-        self.progress_buf = torch.zeros(n, device=dev, dtype=torch.long)
-        self.randomize_buf = torch.zeros(self.num_envs, device=dev, dtype=torch.long)
-        self.actions = torch.zeros((n, self.num_actions), device=dev, dtype=torch.float)
-        import math
-        self._clamp_obs = math.isfinite(float(self.clip_obs))
-        self.obs_clamped = torch.zeros_like(self.obs_buf) if self._clamp_obs else self.obs_buf
-        self._noise = None
-        tb = _abi.TaskBuffers()
-        tb.actions_out, tb.obs = _abi.ptr(self.actions), _abi.ptr(self.obs_buf)
-        tb.obs_clamped = _abi.ptr(self.obs_clamped) if self._clamp_obs else None
-        tb.rew, tb.reset, tb.progress = _abi.ptr(self.rew_buf), _abi.ptr(self.reset_buf), _abi.ptr(self.progress_buf)
-        tb.timeout = _abi.ptr(self.timeout_buf)
-        tb.seed, tb.env_offset = self.seed, self.env_offset
-        self._tb = tb
-
-    env_state_tensors = tuple(k for k in VecTask.env_state_tensors
-                              if k not in ("sensor_tensor", "dof_force_tensor", "potentials", "prev_potentials",
-                                           "up_vec", "heading_vec", "env_props", "randomize_buf_actors")) + (
-        "dof_targets", "rigid_body_states", "net_contact_force_tensor", "_cubeA_state", "_init_cubeA_state")
-
-    # ---------------------------------------------------------------------------------- hot path
-    def _launch_step(self, tb, stream):
-        lib, rp, rv = self._lib, _abi.C.byref(self.reach_params), _abi.C.byref(self._reach_views)
-        _abi.check(lib.mg_reach_pre(self.sim, rp, rv, _abi.C.byref(tb), stream), lib)
-        for _ in range(max(1, self.control_freq_inv)):
-            _abi.check(lib.mg_sim_simulate(self.sim, stream), lib)
-        _abi.check(lib.mg_reach_post(self.sim, rp, rv, _abi.C.byref(tb), None, stream), lib)
+    env_state_tensors = state_tensors(drop=("sensor_tensor", "dof_force_tensor"),
+                                      add=("dof_targets", "rigid_body_states", "net_contact_force_tensor",
+                                           "_cubeA_state", "_init_cubeA_state"))
 
     def compute_observations(self):
         """One observation pass on the current state without stepping (the reference's _refresh +
@@ -218,36 +181,11 @@ class FrankaReachMA(VecTask):
         self._obs_actions = torch.zeros((self.num_actors, self.num_actions), device=self.device)
         tb.actions, tb.noise, tb.out_pack = self._obs_actions.data_ptr(), _abi.ptr(self._noise), None
         tb.step_counter = self.control_steps
-        _abi.check(self._lib.mg_reach_post(self.sim, _abi.C.byref(self.reach_params),
-                                           _abi.C.byref(self._reach_views), _abi.C.byref(tb), None, self._stream()),
+        _abi.check(self._post(self.sim, self._params_ref, self._views_ref, _abi.C.byref(tb), None, self._stream()),
                    self._lib)
         for t, k in zip((self.rew_buf, self.reset_buf, self.progress_buf, self.timeout_buf), keep):
             t.copy_(k)
         return self.obs_buf
-
-    # ---------------------------------------------------------------------------------- API
-    def reset_idx(self, agent_ids, goal_env_ids=None):
-        """reset_idx(agent_ids) (franka_reach_MA.py:616-679), one launch (``mg_reach_reset_idx``): the envs whose
-        agents are all listed (bincount(agent_ids // A) >= A, a repeated id counting twice) get new cubes, DOF state,
-        targets and zero actuation, and their progress / reset cleared; a partial list resets nothing."""
-        ids = torch.as_tensor(agent_ids, device=self.device).flatten().to(torch.int32).contiguous()
-        if ids.numel() == 0:
-            return
-        self._dyn_covered = None
-        self._reset_ids = ids   # alive until the launch has consumed it
-        tb = self._tb
-        tb.step_counter = self.control_steps
-        tb.noise = _abi.ptr(self._noise)
-        _abi.check(self._lib.mg_reach_reset_idx(self.sim, _abi.C.byref(self.reach_params),
-                                                _abi.C.byref(self._reach_views), _abi.C.byref(tb), ids.data_ptr(),
-                                                int(ids.numel()), self._stream()), self._lib)
-
-    def set_reset_noise(self, noise):
-        """Inject per-env U(0,1) rows (N, 3 T + 9) = [z of each cube (T) | xy of each cube (2 T) | DOF noise (9)], the
-        reference's draw order (franka_reach_MA.py:692, 696, 631), instead of the device RNG."""
-        if noise is not None and tuple(noise.shape) != (self.num_envs, 3 * self.num_targets + 9):
-            raise ValueError(f"reset noise must be {(self.num_envs, 3 * self.num_targets + 9)}, got {tuple(noise.shape)}")
-        super().set_reset_noise(noise)
 
     @property
     def states(self):

@@ -27,7 +27,6 @@ What differs from the reference:
 """
 from __future__ import annotations
 
-import math
 import os
 
 import numpy as np
@@ -38,7 +37,7 @@ from .. import model as M
 from .. import spaces
 from .. import taskdefs
 from ..motion import MotionTable
-from .base.vec_task import VecTask
+from .base.simulate_task import SimulateTask, state_tensors
 
 _TASKS_DIR = os.path.dirname(os.path.abspath(__file__))
 NUM_AMP_OBS_PER_STEP = _abi.MG_AMP_OBS
@@ -82,18 +81,15 @@ def _motion_path(env) -> str:
     return path
 
 
-class HumanoidAMP(VecTask):
+class HumanoidAMP(SimulateTask):
     task_name = "HumanoidAMP"
-    supports_host_pipeline = False
-    steps_through_simulate = True   # gym.simulate is mg_sim_simulate: link forces (apply_rigid_body_force_tensors)
+    entry = "mg_amp"
     acquires_dof_force = True   # humanoid_amp_base.py:88-89
 
     def __init__(self, cfg, rl_device, sim_device, graphics_device_id, headless, virtual_screen_capture=False,
                  force_render=False):
+        self._refuse_randomize(cfg)
         env = cfg["env"]
-        if bool((cfg.get("task", {}) or {}).get("randomize", False)):
-            raise NotImplementedError("HumanoidAMP: task.randomize is not built for this task (domain randomization "
-                                      "runs inside the fused step kernels, which this task does not use)")
         self._pd_control = bool(env["pdControl"])
         self.power_scale = env["powerScale"]
         self.camera_follow = env.get("cameraFollow", False)
@@ -135,12 +131,6 @@ class HumanoidAMP(VecTask):
         self.num_bodies = nb = len(spec.bodies)
         self.num_actors = N
         self.sim_params = taskdefs.sim_params(self.cfg, taskdefs.TASK_INFO["HumanoidAMP"][5], 1)
-        self._model_np = _abi.model_bytes(spec)
-        torch.cuda.set_device(self.device_id)
-        h = _abi.C.c_void_p()
-        _abi.check(self._lib.mg_sim_create(self._model_np.ctypes.data, _abi.C.byref(self.sim_params), N,
-                                           self.device_id, _abi.C.byref(h)), self._lib)
-        self.sim = h
         dev, f = self.device, torch.float32
         self.dof_names = list(spec.dof_names)
         self._key_body_ids = torch.tensor(list(ap.key_body), device=dev, dtype=torch.long)
@@ -186,8 +176,7 @@ class HumanoidAMP(VecTask):
         v.dof_force, v.sensors = _abi.ptr(self.dof_force_tensor), _abi.ptr(self.sensor_tensor)
         v.rigid_body_states = _abi.ptr(self._rigid_body_state)
         v.net_contact_forces = _abi.ptr(self.net_contact_force_tensor)
-        self._views = v
-        _abi.check(self._lib.mg_sim_bind(self.sim, _abi.C.byref(v)), self._lib)
+        self._create_sim_handle(spec, v)
         # the motion table (humanoid_amp.py:139-144), on the device once
         self._motion_lib = ml = MotionTable(self._motion_file, list(ap.key_body), nd)
         self._motion_frames, self._motion_index, self._motion_time = ml.to_device(dev)
@@ -197,43 +186,16 @@ class HumanoidAMP(VecTask):
         av.motion_frames, av.motion_index = _abi.ptr(self._motion_frames), _abi.ptr(self._motion_index)
         av.motion_time = _abi.ptr(self._motion_time)
         av.num_motions, av.num_frames = ml.num_motions(), int(self._motion_frames.shape[0])
-        self._amp_views = av
+        self._bind_task(ap, av)
 
-    def allocate_buffers(self):
-        dev, n = self.device, self.num_envs
-        self.obs_buf = torch.zeros((n, self.num_obs), device=dev, dtype=torch.float)
-        self.states_buf = torch.zeros((n, self.num_states), device=dev, dtype=torch.float)
-        self.rew_buf = torch.zeros(n, device=dev, dtype=torch.float)
-        self.reset_buf = torch.ones(n, device=dev, dtype=torch.long)
-        self.timeout_buf = torch.zeros(n, device=dev, dtype=torch.bool)
-        self.progress_buf = torch.zeros(n, device=dev, dtype=torch.long)
-        self.randomize_buf = torch.zeros(n, device=dev, dtype=torch.long)
-        self.actions = torch.zeros((n, self.num_actions), device=dev, dtype=torch.float)
-        self._clamp_obs = math.isfinite(float(self.clip_obs))
-        self.obs_clamped = torch.zeros_like(self.obs_buf) if self._clamp_obs else self.obs_buf
-        self._noise = None
-        tb = _abi.TaskBuffers()
-        tb.actions_out, tb.obs = _abi.ptr(self.actions), _abi.ptr(self.obs_buf)
-        tb.obs_clamped = _abi.ptr(self.obs_clamped) if self._clamp_obs else None
-        tb.rew, tb.reset, tb.progress = _abi.ptr(self.rew_buf), _abi.ptr(self.reset_buf), _abi.ptr(self.progress_buf)
-        tb.timeout = _abi.ptr(self.timeout_buf)
-        tb.seed, tb.env_offset = self.seed, self.env_offset
-        self._tb = tb
-
-    env_state_tensors = tuple(k for k in VecTask.env_state_tensors
-                              if k not in ("potentials", "prev_potentials", "up_vec", "heading_vec",
-                                           "env_props", "randomize_buf_actors")) + (
-        "dof_targets", "net_contact_force_tensor", "rigid_body_states", "_amp_obs_buf", "_terminate_buf")
-    env_state_scalars = VecTask.env_state_scalars + ("_demo_calls",)
+    env_state_tensors = state_tensors(add=("dof_targets", "net_contact_force_tensor", "rigid_body_states",
+                                           "_amp_obs_buf", "_terminate_buf"))
+    env_state_scalars = SimulateTask.env_state_scalars + ("_demo_calls",)
 
     # ---------------------------------------------------------------------------------- hot path
     def _launch_step(self, tb, stream):
-        lib, ap, av = self._lib, _abi.C.byref(self.amp_params), _abi.C.byref(self._amp_views)
         tb.noise = None   # the step draws nothing; reset noise belongs to reset_idx
-        _abi.check(lib.mg_amp_pre(self.sim, ap, av, _abi.C.byref(tb), stream), lib)
-        for _ in range(max(1, self.control_freq_inv)):
-            _abi.check(lib.mg_sim_simulate(self.sim, stream), lib)
-        _abi.check(lib.mg_amp_post(self.sim, ap, av, _abi.C.byref(tb), None, stream), lib)
+        super()._launch_step(tb, stream)
 
     def post_step_extras(self):
         self.extras["terminate"] = self._terminate_buf                               # humanoid_amp_base.py:384
@@ -251,22 +213,15 @@ class HumanoidAMP(VecTask):
         """reset_idx(env_ids) (humanoid_amp.py:146-256), one launch (``mg_amp_reset_idx``): per ``stateInit`` the
         listed envs get the default pose or a pose sampled from the motion table, ``progress = reset = terminate = 0``,
         their observation row and their whole AMP history."""
-        ids = torch.as_tensor(env_ids, device=self.device).flatten().to(torch.int32).contiguous()
-        if ids.numel() == 0:
-            return
-        self._dyn_covered = None
-        self._reset_ids = ids   # alive until the launch has consumed it
-        tb = self._tb
-        tb.step_counter = self.control_steps
-        noise = self._noise_by_id
-        if noise is not None and tuple(noise.shape) != (int(ids.numel()), _abi.MG_AMP_NOISE_COLS):
-            raise ValueError(f"reset noise must be {(int(ids.numel()), _abi.MG_AMP_NOISE_COLS)} for this id list, "
+        super().reset_idx(env_ids)
+        self._tb.noise = None
+
+    def _reset_noise(self, n):
+        noise = self._noise_by_id   # rows by list position, not by env
+        if noise is not None and tuple(noise.shape) != (n, _abi.MG_AMP_NOISE_COLS):
+            raise ValueError(f"reset noise must be {(n, _abi.MG_AMP_NOISE_COLS)} for this id list, "
                              f"got {tuple(noise.shape)}")
-        tb.noise = _abi.ptr(noise)
-        _abi.check(self._lib.mg_amp_reset_idx(self.sim, _abi.C.byref(self.amp_params),
-                                              _abi.C.byref(self._amp_views), _abi.C.byref(tb), ids.data_ptr(),
-                                              int(ids.numel()), self._stream()), self._lib)
-        tb.noise = None
+        return noise
 
     def set_reset_noise(self, noise):
         """Inject U(0,1) rows (n, 3) = [hybrid | motion | phase], one per id of the NEXT ``reset_idx`` calls' lists (by
@@ -290,7 +245,7 @@ class HumanoidAMP(VecTask):
             if tuple(noise.shape) != (num_samples, 2):
                 raise ValueError(f"demo noise must be {(num_samples, 2)}, got {tuple(noise.shape)}")
         self._demo_noise = noise
-        _abi.check(self._lib.mg_amp_obs_demo(_abi.C.byref(self.amp_params), _abi.C.byref(self._amp_views),
+        _abi.check(self._lib.mg_amp_obs_demo(self._params_ref, self._views_ref,
                                              _abi.ptr(noise), self.seed, self._demo_calls,
                                              self._amp_obs_demo_buf.data_ptr(), num_samples, self._stream()),
                    self._lib)

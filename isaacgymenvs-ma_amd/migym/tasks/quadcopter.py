@@ -23,27 +23,27 @@ What differs from the reference:
 """
 from __future__ import annotations
 
-import math
-
 import torch
 
 from .. import _abi
 from .. import model as M
 from .. import taskdefs
-from .base.vec_task import VecTask
+from .base.simulate_task import SimulateTask, state_tensors
 
 
-class Quadcopter(VecTask):
+class Quadcopter(SimulateTask):
+    """``reset_idx(env_ids)`` (quadcopter.py:280-299): the listed envs get their DOF state and root row from the initial
+    state, x, y += U(-1.5, 1.5), z += U(-0.2, 1.5), DOF positions U(-0.2, 0.2), velocities 0, ``reset_buf = 0`` and
+    ``progress_buf = 0``.  Thrusts, forces and targets are cleared by pre_physics_step, for the envs it resets itself.
+    ``set_reset_noise``: per-env U(0,1) rows (N, 11) = [x | y | z | dof position 8], the reference's draw order
+    (quadcopter.py:289-294)."""
     task_name = "Quadcopter"
-    supports_host_pipeline = False
-    steps_through_simulate = True
+    entry = "mg_quadcopter"
 
     def __init__(self, cfg, rl_device, sim_device, graphics_device_id, headless, virtual_screen_capture=False,
                  force_render=False):
+        self._refuse_randomize(cfg)
         env = cfg["env"]
-        if bool((cfg.get("task", {}) or {}).get("randomize", False)):
-            raise NotImplementedError("Quadcopter: task.randomize is not built for this task (domain randomization "
-                                      "runs inside the fused step kernels, which this task does not use)")
         self.max_episode_length = env["maxEpisodeLength"]
         self.debug_viz = env.get("enableDebugVis", False)   # ignored: there is no viewer
         env["numObservations"] = _abi.MG_QUAD_OBS
@@ -61,12 +61,6 @@ class Quadcopter(VecTask):
         self.num_bodies = nb = len(spec.bodies)
         self.num_actors = N
         self.sim_params = taskdefs.sim_params(self.cfg, taskdefs.QUADCOPTER_MAX_CONTACTS, 1)
-        self._model_np = _abi.model_bytes(spec)
-        torch.cuda.set_device(self.device_id)
-        h = _abi.C.c_void_p()
-        _abi.check(self._lib.mg_sim_create(self._model_np.ctypes.data, _abi.C.byref(self.sim_params), N,
-                                           self.device_id, _abi.C.byref(h)), self._lib)
-        self.sim = h
         dev, f = self.device, torch.float32
         self.initial_root_states = torch.tensor(list(qp.init_root), device=dev, dtype=f).repeat(N, 1).contiguous()
         self.root_states = self.initial_root_states.clone()
@@ -92,48 +86,16 @@ class Quadcopter(VecTask):
         v.dof_actuation, v.dof_targets = _abi.ptr(self.dof_actuation), _abi.ptr(self.dof_position_targets)
         # gym.apply_rigid_body_force_tensors(sim, forces, None, LOCAL_SPACE) (quadcopter.py:330)
         v.rb_forces, v.rb_force_space = _abi.ptr(self.forces), _abi.MG_LOCAL_SPACE
-        self._views = v
         self.rb_forces = self.forces
-        _abi.check(self._lib.mg_sim_bind(self.sim, _abi.C.byref(v)), self._lib)
+        self._create_sim_handle(spec, v)
         _abi.check(self._lib.mg_sim_set_link_forces(self.sim, 1), self._lib)
         qv = _abi.QuadcopterViews()
         qv.thrusts, qv.dof_targets = _abi.ptr(self.thrusts), _abi.ptr(self.dof_position_targets)
         qv.forces = _abi.ptr(self.forces)
-        self._quad_views = qv
+        self._bind_task(qp, qv, noise_shape=(N, _abi.MG_QUAD_NOISE_COLS))
 
-    def allocate_buffers(self):
-        dev, n = self.device, self.num_envs
-        self.obs_buf = torch.zeros((n, self.num_obs), device=dev, dtype=torch.float)
-        self.states_buf = torch.zeros((n, self.num_states), device=dev, dtype=torch.float)
-        self.rew_buf = torch.zeros(n, device=dev, dtype=torch.float)
-        self.reset_buf = torch.ones(n, device=dev, dtype=torch.long)
-        self.timeout_buf = torch.zeros(n, device=dev, dtype=torch.bool)
-        self.progress_buf = torch.zeros(n, device=dev, dtype=torch.long)
-        self.randomize_buf = torch.zeros(n, device=dev, dtype=torch.long)
-        self.actions = torch.zeros((n, self.num_actions), device=dev, dtype=torch.float)
-        self._clamp_obs = math.isfinite(float(self.clip_obs))
-        self.obs_clamped = torch.zeros_like(self.obs_buf) if self._clamp_obs else self.obs_buf
-        self._noise = None
-        tb = _abi.TaskBuffers()
-        tb.actions_out, tb.obs = _abi.ptr(self.actions), _abi.ptr(self.obs_buf)
-        tb.obs_clamped = _abi.ptr(self.obs_clamped) if self._clamp_obs else None
-        tb.rew, tb.reset, tb.progress = _abi.ptr(self.rew_buf), _abi.ptr(self.reset_buf), _abi.ptr(self.progress_buf)
-        tb.timeout = _abi.ptr(self.timeout_buf)
-        tb.seed, tb.env_offset = self.seed, self.env_offset
-        self._tb = tb
-
-    env_state_tensors = tuple(k for k in VecTask.env_state_tensors
-                              if k not in ("sensor_tensor", "dof_force_tensor", "potentials", "prev_potentials",
-                                           "up_vec", "heading_vec", "env_props", "randomize_buf_actors")) + (
-        "thrusts", "dof_position_targets", "forces")
-
-    # ---------------------------------------------------------------------------------- hot path
-    def _launch_step(self, tb, stream):
-        lib, qp, qv = self._lib, _abi.C.byref(self.quadcopter_params), _abi.C.byref(self._quad_views)
-        _abi.check(lib.mg_quadcopter_pre(self.sim, qp, qv, _abi.C.byref(tb), stream), lib)
-        for _ in range(max(1, self.control_freq_inv)):
-            _abi.check(lib.mg_sim_simulate(self.sim, stream), lib)
-        _abi.check(lib.mg_quadcopter_post(self.sim, qp, qv, _abi.C.byref(tb), None, stream), lib)
+    env_state_tensors = state_tensors(drop=("sensor_tensor", "dof_force_tensor"),
+                                      add=("thrusts", "dof_position_targets", "forces"))
 
     # ---------------------------------------------------------------------------------- API
     def apply_rigid_body_force_tensors(self, forces, torques=None, space=_abi.MG_LOCAL_SPACE):
@@ -145,28 +107,4 @@ class Quadcopter(VecTask):
                              "(quadcopter.py:330): space must be LOCAL_SPACE")
         super().apply_rigid_body_force_tensors(forces, torques, space)
         self.forces = forces
-        self._quad_views.forces = forces.data_ptr()
-
-    def reset_idx(self, env_ids, goal_env_ids=None):
-        """reset_idx(env_ids) (quadcopter.py:280-299), one launch (``mg_quadcopter_reset_idx``): the listed envs get
-        their DOF state and root row from the initial state, x, y += U(-1.5, 1.5), z += U(-0.2, 1.5), DOF positions
-        U(-0.2, 0.2), velocities 0, ``reset_buf = 0`` and ``progress_buf = 0``.  Thrusts, forces and targets are
-        cleared by pre_physics_step, for the envs it resets itself."""
-        ids = torch.as_tensor(env_ids, device=self.device).flatten().to(torch.int32).contiguous()
-        if ids.numel() == 0:
-            return
-        self._reset_ids = ids   # alive until the launch has consumed it
-        tb = self._tb
-        tb.step_counter = self.control_steps
-        tb.noise = _abi.ptr(self._noise)
-        _abi.check(self._lib.mg_quadcopter_reset_idx(self.sim, _abi.C.byref(self.quadcopter_params),
-                                                     _abi.C.byref(self._quad_views), _abi.C.byref(tb), ids.data_ptr(),
-                                                     int(ids.numel()), self._stream()), self._lib)
-
-    def set_reset_noise(self, noise):
-        """Inject per-env U(0,1) rows (N, 11) = [x | y | z | dof position 8], the reference's draw order
-        (quadcopter.py:289-294), instead of the device RNG."""
-        want = (self.num_envs, _abi.MG_QUAD_NOISE_COLS)
-        if noise is not None and tuple(noise.shape) != want:
-            raise ValueError(f"reset noise must be {want}, got {tuple(noise.shape)}")
-        super().set_reset_noise(noise)
+        self._task_views.forces = forces.data_ptr()

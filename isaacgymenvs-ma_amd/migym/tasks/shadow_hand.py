@@ -59,12 +59,6 @@ class ShadowHand(VecTask):
         self.num_actors = self.num_envs
         self.sim_params = taskdefs.sim_params(self.cfg, max_contacts, 1)
         self.task_params = tp = taskdefs.task_params("ShadowHand", self.cfg, spec)
-        self._model_np = _abi.model_bytes(spec)
-        torch.cuda.set_device(self.device_id)
-        h = _abi.C.c_void_p()
-        _abi.check(self._lib.mg_sim_create(self._model_np.ctypes.data, _abi.C.byref(self.sim_params),
-                                           self.num_envs, self.device_id, _abi.C.byref(h)), self._lib)
-        self.sim = h
         dev, f, N, nd = self.device, torch.float32, self.num_envs, self.num_dof
         # actor root states [hand, object, goal] per env (shadow_hand.py:356-384, 400-405)
         self.root_state_tensor = torch.zeros((N * 3, 13), device=dev, dtype=f)
@@ -111,8 +105,7 @@ class ShadowHand(VecTask):
         self.object_rb_handles = torch.tensor([self.num_shadow_hand_bodies], device=dev, dtype=torch.long)
         self.object_rb_masses = torch.tensor([tp.object_rb_mass], device=dev, dtype=f)
         v.rb_forces, v.rb_force_space = _abi.ptr(self.rb_forces), _abi.MG_LOCAL_SPACE
-        self._views = v
-        _abi.check(self._lib.mg_sim_bind(self.sim, _abi.C.byref(v)), self._lib)
+        self._create_sim_handle(spec, v)
 
     env_state_tensors = VecTask.env_state_tensors + (
         "root_state_tensor", "rigid_body_states", "prev_targets", "cur_targets", "goal_states", "reset_goal_buf",

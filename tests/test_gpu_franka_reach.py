@@ -77,6 +77,7 @@ class ReachSim:
         rv.dof_targets, rv.dof_actuation = self.tgt.data_ptr(), self.act.data_ptr()
         self.rv = rv
         self.noise = None
+        self.out_pack = None   # (N*A, num_obs + 2) [clamped obs | rew | reset], the output gather's message rows
 
     def tb(self, seed=0, step=0, env_offset=0):
         b = _abi.TaskBuffers()
@@ -84,6 +85,7 @@ class ReachSim:
         b.obs, b.obs_clamped, b.rew = self.obs.data_ptr(), self.obs_clamped.data_ptr(), self.rew.data_ptr()
         b.reset, b.progress, b.timeout = self.reset.data_ptr(), self.progress.data_ptr(), self.timeout.data_ptr()
         b.noise = None if self.noise is None else self.noise.data_ptr()
+        b.out_pack = None if self.out_pack is None else self.out_pack.data_ptr()
         b.seed, b.step_counter, b.env_offset = seed, step, env_offset
         return b
 
@@ -129,9 +131,12 @@ class ReachSim:
 def test_post_replays_the_reference(lib, A, T, N):
     """all 6 recorded steps through the state-injection path with the recorded draws: obs, reset, progress, cubes,
     q, qd, the position and effort controls bit-equal, the reward by the 1e-4 rule; punished agents and partly done
-    envs included (asserted by tests/test_franka_reach_host.py on the same file)"""
+    envs included (asserted by tests/test_franka_reach_host.py on the same file).  The gather's message rows
+    (out_pack): the clip of the recorded observations, the launch's own reward bit for bit, the recorded reset."""
     g = R.golden()
     s = ReachSim(lib, A, T, N)
+    no = s.rp.num_obs
+    s.out_pack = torch.full((N * A, no + 2), float("nan"), device=DEV)
     nd, nb, grip, hand = s.nd, s.nb, s.rp.eef_body, s.rp.hand_body
     st0 = R.golden_state0(g, A, T, N)
     s.cube.copy_(dev(st0["cube"]))
@@ -168,6 +173,11 @@ def test_post_replays_the_reference(lib, A, T, N):
         print(f"A={A} T={T} step {t}: max |rew - ref| = {worst:.3g}")
         assert R.reward_close(rew, g[pre + "rew"]).all(), f"step {t}: reward off by {worst:.3g}"
         assert np.array_equal(s.obs_clamped.cpu().numpy(), np.clip(obs, -p["clip_obs"], p["clip_obs"]))
+        pack = s.out_pack.cpu().numpy()
+        want_obs = np.clip(g[pre + "obs"], -p["clip_obs"], p["clip_obs"])
+        assert np.array_equal(pack[:, :no], want_obs), f"step {t}: out_pack's observation columns"
+        assert np.array_equal(pack[:, no], rew), f"step {t}: out_pack's reward column is not rew_buf"
+        assert np.array_equal(pack[:, no + 1], g[pre + "reset"].astype(np.float32)), f"step {t}: pack reset"
         tmo = (g[pre + "progress"] >= p["max_episode_length"] - 1) & (g[pre + "reset"] != 0)
         assert np.array_equal(s.timeout.cpu().numpy(), tmo)
         assert (s.dof.cpu().numpy() == 0).all(), "the sim's own DOF state is not touched under state injection"
@@ -408,6 +418,7 @@ def test_whole_step_equals_the_three_launches(lib):
     assert env.num_obs == 25 and env.obs_buf.shape == (27, 25) and env.num_agents == 3
     assert (env.progress_buf == 0).all() and (env.reset_buf == 0).all(), "the constructor resets every env"
     s = ReachSim(lib, A, T, N, episodeLength=150)
+    s.out_pack = torch.full((N * A, 27), float("nan"), device=DEV)
     rng = np.random.default_rng(9)
     # start the hand-driven sim from the task's state after its constructor
     s.dof.copy_(env.dof_state)
@@ -440,6 +451,8 @@ def test_whole_step_equals_the_three_launches(lib):
         assert torch.equal(env.dof_targets, s.tgt) and torch.equal(env._cubeA_state, s.cube)
         assert torch.equal(env.rigid_body_states, s.rbs) and torch.equal(env.actions, s.actions_out)
         assert torch.isfinite(env.obs_buf).all() and extras["time_outs"].dtype == torch.bool
+        want_pack = torch.cat([s.obs_clamped, s.rew.view(-1, 1), s.reset.view(-1, 1).to(torch.float32)], 1)
+        assert torch.equal(s.out_pack, want_pack), f"step {t}: out_pack is not [clamped obs | rew | reset]"
         if t == 2:
             p = env.progress_buf.view(N, A).cpu().numpy()
             assert (p[[0, 8]] == 0).all() and (p[1:8] == 3).all()

@@ -2,7 +2,8 @@
 DESIGN.md §14), against the reference's own trace (tests/golden/trace_quadcopter.npz) and the oracle.
 
   * pre and post replay the traces: integers, DOF state, root rows, thrusts, targets and forces bit for bit, floats
-    within the project's 1e-4 (the measured maximum is printed).
+    within the project's 1e-4 (the measured maximum is printed); the gather's message rows (out_pack) equal
+    [clamped obs | rew | reset] of the same launch bit for bit.
   * The device RNG equals its host twin at env_offset 0 and 5.
   * reset_idx with a repeated id changes the listed envs only.
   * Quadcopter.step equals the three launches by hand, bit for bit, over 8 steps with resets at N = 67; a caller's
@@ -60,6 +61,7 @@ class QuadSim:
         self.qv = _abi.QuadcopterViews()
         self.qv.thrusts, self.qv.dof_targets, self.qv.forces = self.thr.data_ptr(), self.tgt.data_ptr(), self.frc.data_ptr()
         self.noise = None
+        self.out_pack = None   # (N, 23) [clamped obs | rew | reset], the output gather's message rows
 
     def tb(self, step=0, seed=0, env_offset=0):
         b = _abi.TaskBuffers()
@@ -67,7 +69,7 @@ class QuadSim:
             self.obs.data_ptr(), self.obs_c.data_ptr()
         b.rew, b.reset, b.progress, b.timeout = self.rew.data_ptr(), self.reset.data_ptr(), self.progress.data_ptr(), \
             self.timeout.data_ptr()
-        b.noise = _abi.ptr(self.noise)
+        b.noise, b.out_pack = _abi.ptr(self.noise), _abi.ptr(self.out_pack)
         b.seed, b.step_counter, b.env_offset = seed, step, env_offset
         return b
 
@@ -104,6 +106,7 @@ def np_(t):
 def test_pre_and_post_replay_the_reference_trace(lib, N):
     g = R.golden()
     s = QuadSim(lib, N)
+    s.out_pack = torch.full((N, 23), float("nan"), device=DEV)
     for name, t in (("dof_position_targets", s.tgt), ("thrusts", s.thr), ("forces", s.frc), ("root_states", s.root),
                     ("dof_states", s.dof)):
         t.copy_(dev(g[f"N{N}_{name}_0"]))
@@ -145,6 +148,9 @@ def test_pre_and_post_replay_the_reference_trace(lib, N):
         for got, ref in ((s.obs, k("obs")), (s.obs_c, k("obs_clamped")), (s.rew, k("rew"))):
             assert R.close(np_(got), ref).all(), f"step {t}"
             worst = max(worst, float(np.abs(np_(got).astype(np.float64) - ref).max()))
+        want_pack = np.concatenate([np_(s.obs_c), np_(s.rew)[:, None], np_(s.reset).astype(F)[:, None]], 1)
+        np.testing.assert_array_equal(np_(s.out_pack), want_pack,
+                                      err_msg=f"step {t}: out_pack is not [clamped obs | rew | reset]")
     print(f"N={N}: largest float difference from the reference trace {worst:.3g}")
     s.close()
 

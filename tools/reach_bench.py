@@ -174,7 +174,7 @@ def main():
         for p, f in paths.items():
             times[p] += timed(f, min(50, a.steps - start))
     # the three launches of (a), one by one
-    lib, rp, rv, tb = env._lib, _abi.C.byref(env.reach_params), _abi.C.byref(env._reach_views), env._tb
+    lib, rp, rv, tb = env._lib, _abi.C.byref(env.reach_params), _abi.C.byref(env._task_views), env._tb
     tb.actions = acts[0].data_ptr()
     st = env._stream()
     single = {
