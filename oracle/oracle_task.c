@@ -360,8 +360,18 @@ int orc_env_step(const mg_model* m, const mg_sim_params* p, const mg_task_params
                                                                     : a * tp->motor_effort[i] * tp->power_scale;
       }
   }
-  /* gym.simulate x controlFrequencyInv (vec_task.py:381-384) */
+  /* gym.simulate x controlFrequencyInv (vec_task.py:381-384); the views orc_simulate takes, and the actors'
+   * env_props rows when bound (the domain-randomized step: mg_env_step reads them too) */
+  mg_state_views sv;
+  memset(&sv, 0, sizeof(sv));
+  sv.root_states = v->root_states;
+  sv.dof_state = v->dof_state;
+  sv.dof_actuation = eff;
+  sv.sensors = v->sensors;
+  sv.dof_force = v->dof_force;
+  sv.env_props = v->env_props;
+  sv.env_props_stride = v->env_props_stride;
   for (int k = 0; k < (tp->control_freq_inv > 1 ? tp->control_freq_inv : 1); k++)
-    orc_simulate(m, p, n, v->root_states, v->dof_state, eff, v->sensors, v->dof_force, threads);
+    orc_simulate_views(m, p, n, &sv, threads);
   return orc_post_physics(tp, v, tb, n);
 }

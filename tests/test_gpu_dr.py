@@ -6,6 +6,11 @@
 * the physics kernels with an env_props table (the domain-randomized instances) vs the oracle applying
   the same rows to its fp64 model, for Ant and ShadowHand, from identical random states — the bars of
   tests/test_gpu_parity.py / test_gpu_hand.py.
+* the same on the capacities those two do not reach (Cartpole's 8 lanes, the Humanoid's 32 in both layouts and
+  under TGS, the three tree capacities), sensors and DOF forces included; the fused mg_env_step with env_props bound
+  (k_env_step<DR>, k_hand_step<DR>) teacher-forced against the oracle by the rules of the plain fused tests; and the
+  DR instance on rows of defaults against the plain instance.  Inputs and rules: tests/dr_ref.py; the oracle's fp32
+  twin through the same rules on the CPU: tests/test_dr_parity_host.py.
 * make() with task.randomize for Ant / Humanoid / ShadowHand: the shipped randomization_params run
   through the fused step, properties land in their ranges, and the per-env rows differ.
 """
@@ -20,6 +25,8 @@ import copy
 import parity_stats as PS
 import pyoracle as O
 from migym import _abi, configs, model as M, taskdefs
+import dr_ref as DRR
+from dr_ref import _dr_explained, _physics_sensitive, agreement, random_props   # shared with tests/test_dr_parity_host.py
 from dr_trace import defaults, layout
 from test_dr import replay_dr_trace
 
@@ -64,78 +71,6 @@ class DeviceBackend:
 
 def test_dr_trace_matches_reference_gpu(lib):
     replay_dr_trace(DeviceBackend(lib))
-
-
-def random_props(spec, n, rng):
-    """env_props rows with every supported property perturbed"""
-    stride, offs = layout(spec)
-    props = np.tile(defaults(spec), (n, 1))
-    nn = len(spec.nodes)
-    for i in range(nn):
-        r = props[:, _abi.MG_EP_NODE_WIDTH * i:_abi.MG_EP_NODE_WIDTH * (i + 1)]
-        r[:, 0] *= rng.uniform(0.5, 1.5, n)          # mass
-        r[:, 1] *= rng.uniform(0.5, 1.5, n)          # armature
-        r[:, 2] *= rng.uniform(0.3, 3.0, n)          # damping
-        r[:, 3] *= rng.uniform(0.5, 1.5, n)          # stiffness
-        r[:, 4] += rng.normal(0, 0.02, n)            # lower
-        r[:, 5] += rng.normal(0, 0.02, n)            # upper
-        r[:, 6] *= rng.uniform(0.75, 1.5, n)         # drive kp
-        r[:, 8] *= rng.uniform(0.3, 3.0, n)          # frictionloss (the hand's 0.001; 0 elsewhere)
-    props[:, offs[1]:offs[1] + len(spec.geoms)] *= rng.uniform(0.3, 1.3, (n, len(spec.geoms)))
-    nt = len(spec.tendons)
-    props[:, offs[2]:offs[2] + 2 * nt] *= rng.uniform(0.3, 3.0, (n, 2 * nt))
-    if spec.obj:
-        props[:, offs[3] + 0] *= rng.uniform(0.5, 1.5, n)
-        props[:, offs[3] + 1] *= rng.uniform(0.3, 1.3, n)
-        props[:, offs[3] + 2] = rng.uniform(0.9, 1.1, n)
-    return props
-
-
-def agreement(a, b, atol, rtol):
-    a = a.reshape(a.shape[0], -1)
-    b = b.reshape(b.shape[0], -1)
-    return ((np.abs(a - b) <= atol + rtol * np.abs(b)).all(axis=1)).mean()
-
-
-def _physics_sensitive(mnp, sp, pre, i, checks, hand, eps=1e-6, ratio=0.25):
-    """the oracle's own sensitivity at env i: its physics step alone from `pre`, once as given and once with the
-    positions moved by eps; True if some element outside its tolerance moves by >= ratio x the largest such gap
-    (e.g. several capsules a centimetre or two inside the egg, whose depenetration a 1e-6 m change moves by 1e-3)"""
-    outs = []
-    for pert in (0.0, eps):
-        g = PS.env_slice(pre, i)
-        if hand:
-            g.root[:, 1, 0:3] += pert
-        else:
-            g.root[:, 0:3] += pert
-        g.dof[..., 0] += pert
-        O.lib().orc_simulate_views(mnp.ctypes.data, C.byref(sp), 1, C.byref(g.views()), 1)
-        outs.append(g)
-    for name, a, b, atol, rtol, pick in checks:
-        ai, bi = np.ravel(a[i]).astype(np.float64), np.ravel(b[i]).astype(np.float64)
-        diff = np.abs(ai - bi)
-        out = diff > atol + rtol * np.abs(bi)   # the elements outside their tolerance
-        if not out.any():
-            continue
-        moved = np.abs(np.ravel(pick(outs[1])).astype(np.float64) - np.ravel(pick(outs[0])))[out].max()
-        if moved >= ratio * diff[out].max():
-            return True
-    return False
-
-
-def _dr_explained(test, mnp, sp, pre, checks, hand):
-    """every env within each check's tolerance unless orc_step_flips (with the env's own env_props row) puts its
-    step at a discontinuity or the oracle is itself sensitive there (_physics_sensitive, capped at 1%); the
-    exemptions' reach is capped (tests/parity_stats.py).  checks: (name, gpu, oracle, atol, rtol, pick) with
-    pick(host) selecting the quantity from a one-env oracle copy"""
-    bad = np.zeros(pre.n, bool)
-    for name, a, b, atol, rtol, _ in checks:
-        eb = PS.env_bad(a, b, atol, rtol)
-        PS.record(test, name, a, b, envs_outside=int(eb.sum()), atol=atol, rtol=rtol)
-        bad |= eb
-    flags = PS.step_flags(mnp, sp, pre)
-    PS.assert_steps_explained(test, bad[None], flags[None],
-                              sens=lambda t, i: _physics_sensitive(mnp, sp, pre, i, checks, hand))
 
 
 @pytest.mark.parametrize("layout", ["auto", "compact"])
@@ -227,6 +162,202 @@ def test_dr_physics_matches_oracle_hand(lib, kind, solver):
                    ("object twist", rg[:, 1, 7:13], h.root[:, 1, 7:13], 2e-3, 2e-3, lambda g: g.root[0, 1, 7:13]),
                    ("dof pos", dg[..., 0], h.dof[..., 0], 2e-4, 0, lambda g: g.dof[0, :, 0]),
                    ("dof vel", dg[..., 1], h.dof[..., 1], 2e-3, 2e-3, lambda g: g.dof[0, :, 1])], hand=True)
+
+
+# -------------------------------------------------------------------------- the fused step under domain randomization
+# k_env_step<DR> / k_hand_step<DR> are what a run with task.randomize launches every step.  The cases (tests/dr_ref.py
+# fused_case: random_props' rows, the oracle rolled on with them, time limits inside the run) go through the harness
+# of the plain fused tests unchanged -- DevEnv / DevHandEnv bind the host's env_props, and the deepcopy / env_slice
+# copies that step_flags, the sensitivity fallback and the fp32 twin take carry the rows.  tests/test_dr_parity_host.py
+# puts the oracle's fp32 twin through the same rule on the CPU.
+def _gpu_final_step(lib, spec, sp, tp, pre, hand, props):
+    """the observations after one mg_env_step from `pre` (dr_ref.final_step_input) with the rows bound or not"""
+    from test_gpu_hand import DevHandEnv
+    from test_gpu_parity import DevEnv
+    g = copy.deepcopy(pre)
+    if not props:
+        g.env_props = None
+    e = (DevHandEnv if hand else DevEnv)(g)
+    mnp = M.pack_model(spec)
+    sim = C.c_void_p()
+    _abi.check(lib.mg_sim_create(mnp.ctypes.data, C.byref(sp), g.n, 0, C.byref(sim)), lib)
+    try:
+        _abi.check(lib.mg_sim_bind(sim, C.byref(e.views())), lib)
+        _abi.check(lib.mg_env_step(sim, C.byref(tp), C.byref(e.buffers(seed=DRR.STEP_SEED, step=DRR.FUSED_STEPS - 1)),
+                                   torch.cuda.current_stream().cuda_stream), lib)
+        torch.cuda.synchronize()
+    finally:
+        lib.mg_sim_destroy(sim)
+    return e.obs.cpu().numpy()
+
+
+def _assert_props_matter(lib, spec, sp, tp, h0, acts, hand):
+    """the last teacher-forced step once more with env_props unbound, on both sides: fewer than half the envs then
+    end where the domain-randomized step ends (and the device's own DR step does end there)"""
+    pre = DRR.final_step_input(spec, sp, tp, h0, acts)
+    dr = DRR.oracle_final_step(spec, sp, tp, pre, props=True).obs
+    assert agreement(DRR.oracle_final_step(spec, sp, tp, pre, props=False).obs, dr, 2e-3, 2e-3) < 0.5
+    assert agreement(_gpu_final_step(lib, spec, sp, tp, pre, hand, props=False), dr, 2e-3, 2e-3) < 0.5
+    assert agreement(_gpu_final_step(lib, spec, sp, tp, pre, hand, props=True), dr, 2e-3, 2e-3) > 0.9
+
+
+@pytest.mark.parametrize("name,layout", [("Cartpole", "classic"), ("Ant", "classic"), ("Ant", "compact"),
+                                         ("Humanoid", "classic"), ("Humanoid", "compact"), ("MAAnt", "classic"),
+                                         ("Ant-tgs", "classic")])
+def test_dr_fused_env_step_matches_oracle(lib, name, layout, monkeypatch):
+    """mg_env_step with env_props bound (k_env_step<DR>: the 8-, 16- and 32-lane instances, both team layouts, MA-Ant,
+    TGS) against orc_env_step applying the same rows, over 4 teacher-forced control steps with device-RNG resets: the
+    rule and the numbers of test_fused_env_step_matches_oracle"""
+    from test_gpu_parity import _teacher_forced, assert_north_star_rtol, kernel_layout
+    monkeypatch.setenv("MIGYM_LAYOUT", layout)
+    spec, sp, tp, h, acts = DRR.fused_case(name)
+    lanes = {"Cartpole": 8, "Humanoid": 32}.get(DRR.FUSED[name][0], 16)
+    assert kernel_layout(lib, spec, sp, h.n) == (lanes, layout == "compact")
+    h0 = copy.deepcopy(h)
+    res = _teacher_forced(lib, f"test_dr_fused_env_step_matches_oracle[{name}-{layout}]", spec, sp, tp, h,
+                          DRR.FUSED_STEPS, acts, seed=DRR.STEP_SEED)
+    assert_north_star_rtol(res)
+    _assert_props_matter(lib, spec, sp, tp, h0, acts, hand=False)
+
+
+@pytest.mark.parametrize("name", DRR.HAND_FUSED)
+def test_dr_fused_hand_step_matches_oracle(lib, name):
+    """mg_env_step of the ShadowHand with env_props bound (k_hand_step<DR>: block, egg, pen, block under TGS; masses,
+    drives, effort limits, tendons, friction, object mass / friction / scale randomized) against orc_hand_env_step
+    applying the same rows: the rule and the numbers of test_hand_fused_env_step_matches_oracle, 4 steps"""
+    from test_gpu_hand import _hand_teacher_forced
+    spec, sp, tp, h, acts = DRR.fused_case(name)
+    h0 = copy.deepcopy(h)
+    _hand_teacher_forced(lib, f"test_dr_fused_hand_step_matches_oracle[{name}]", spec, sp, tp, h, DRR.FUSED_STEPS, acts,
+                         DRR.STEP_SEED)
+    _assert_props_matter(lib, spec, sp, tp, h0, acts, hand=True)
+
+
+# -------------------------------------------------------------------------- k_simulate<DR> on its other capacities
+def _gpu_simulate_dr(lib, spec, sp, pre, props="rows"):
+    """(result, team lanes, compact) of one mg_sim_simulate of the host `pre` on the device; props: "rows" binds
+    pre.env_props, "defaults" rows of mg_env_props_defaults (the DR instance on the model's own values), None nothing
+    (the plain instance)"""
+    import types
+    mnp = M.pack_model(spec)
+    d = {k: torch.from_numpy(np.array(getattr(pre, k))).to(DEV) for k in ("root", "dof", "act_eff", "sensors", "dof_force")}
+    v = _abi.StateViews()
+    v.root_states, v.dof_state, v.dof_actuation = d["root"].data_ptr(), d["dof"].data_ptr(), d["act_eff"].data_ptr()
+    v.sensors, v.dof_force = d["sensors"].data_ptr(), d["dof_force"].data_ptr()
+    if props == "rows":
+        tp_ = torch.from_numpy(np.array(pre.env_props)).to(DEV)
+    elif props == "defaults":
+        tp_ = _default_rows(lib, mnp, pre.n)
+    if props is not None:
+        v.env_props, v.env_props_stride = tp_.data_ptr(), tp_.shape[1]
+    sim = C.c_void_p()
+    _abi.check(lib.mg_sim_create(mnp.ctypes.data, C.byref(sp), pre.n, 0, C.byref(sim)), lib)
+    try:
+        t, lay = C.c_int32(), C.c_int32()
+        _abi.check(lib.mg_sim_kernel_layout(sim, C.byref(t), C.byref(lay)), lib)
+        _abi.check(lib.mg_sim_bind(sim, C.byref(v)), lib)
+        _abi.check(lib.mg_sim_simulate(sim, torch.cuda.current_stream().cuda_stream), lib)
+        torch.cuda.synchronize()
+    finally:
+        lib.mg_sim_destroy(sim)
+    got = types.SimpleNamespace(**{k: x.cpu().numpy() for k, x in d.items()})
+    for x in vars(got).values():
+        assert np.isfinite(x).all()
+    return got, t.value, lay.value
+
+
+def _default_rows(lib, mnp, n):
+    offs = (C.c_int32 * 4)()
+    stride = lib.mg_env_props_layout(mnp.ctypes.data, offs)
+    row = np.zeros(stride, np.float32)
+    _abi.check(lib.mg_env_props_defaults(mnp.ctypes.data, row.ctypes.data), lib)
+    return torch.from_numpy(row).to(DEV).repeat(n, 1).contiguous()
+
+
+SIM_LANES = {"Cartpole": 8, "Humanoid-pgs": 32, "Humanoid-tgs": 32}
+
+
+@pytest.mark.parametrize("name,layout", [("Cartpole", "classic"), ("Humanoid-pgs", "classic"), ("Humanoid-pgs", "compact"),
+                                         ("Humanoid-tgs", "classic"), ("Humanoid-tgs", "compact")]
+                         + [(k, "classic") for k in DRR.TREE_SIM + ("T16-fixed-tgs",)])
+def test_dr_physics_matches_oracle_other_capacities(lib, name, layout, monkeypatch):
+    """k_simulate<DR> where test_dr_physics_matches_oracle_ant / _hand do not take it: Cartpole's 8-lane instance, the
+    Humanoid's (32, 24, 32, 24, 160) in both layouts and under TGS, and the three tree capacities (self pairs: the
+    friction of a pair averages two randomized shape frictions; more geoms than team lanes: a second round of the
+    lane-per-geom loops reads the rows' geom frictions) -- one mg_sim_simulate from identical states against
+    orc_simulate_views with the same rows, by _dr_explained with the bars of the Ant and hand tests; sensors and DOF
+    forces (which read the randomized damping, stiffness and frictionloss) by tests/tree_physics_ref.py's rule"""
+    monkeypatch.setenv("MIGYM_LAYOUT", layout)
+    spec, sp, pre, ref = DRR.sim_case(name)
+    got, lanes, compact = _gpu_simulate_dr(lib, spec, sp, pre)
+    want = SIM_LANES[name] if name in SIM_LANES else int(name[1:3])
+    assert (lanes, compact) == (want, int(layout == "compact")), (lanes, compact)
+    _dr_explained(f"test_dr_physics_matches_oracle_other_capacities[{name}-{layout}]", M.pack_model(spec), sp, pre,
+                  DRR.sim_checks(spec, got, ref), hand=False)
+    # the properties matter: the same states without them end elsewhere
+    plain, _, _ = _gpu_simulate_dr(lib, spec, sp, pre, props=None)
+    assert agreement(plain.dof[..., 1], ref.dof[..., 1], 2e-3, 2e-3) < 0.5
+
+
+# -------------------------------------------------------------------------- rows of defaults change nothing
+@pytest.mark.parametrize("name", ["Ant", "Humanoid", "hand-block"])
+def test_default_rows_equal_the_plain_instance(lib, name):
+    """env_props bound to rows of mg_env_props_defaults: the DR instance runs on the model's own values -- the inertia
+    scale is mass / mass = 1 (an IEEE division), the averaged friction 0.5 (1 + 1), every node property a copy -- from
+    the same state as the plain instance, independent of the oracle.  The two are separate instantiations of code
+    compiled with FMA contraction on (team_physics.hpp: fp contract(fast)): what the plain one folds at compile time
+    (the scale 1.0f, a null row pointer) the DR one multiplies at run time, so the compiler fuses the sums around
+    them differently, and the results are NOT bit-identical.  Measured on the MI355X: at most 4.5e-8 in
+    a pose, 4.4e-6 in a twist, 8.9e-7 / 1.1e-4 in a DOF position / velocity, 3.7e-4 in a DOF force and 5.3e-3 in a
+    sensor (the Humanoid's, of forces ~1e3); a scratch build with contraction off gave the plain instance's bits in
+    every quantity of all three cases, so contraction is the whole difference.  So every env of the pair is held to
+    the one-step bars of the oracle tests (positions 2e-4, velocities 2e-3 + 2e-3 |v|, DOF forces and sensors 1 % of
+    the batch's largest; the hand's rigid bodies 2e-3 + 2e-3 |x|), with no exemption."""
+    spec, sp, tp, h, acts = DRR.fused_case(name)
+    mnp = M.pack_model(spec)
+    if name == "hand-block":
+        from test_gpu_hand import DevHandEnv
+        h.pre_physics(mnp, tp, seed=DRR.STEP_SEED, step=0)   # PD targets for the drives
+        h.env_props = None                                   # (DevHandEnv would bind the case's random rows)
+        outs = []
+        for rows in (False, True):
+            e = DevHandEnv(h)
+            v = e.views()
+            if rows:
+                tp_ = _default_rows(lib, mnp, h.n)
+                v.env_props, v.env_props_stride = tp_.data_ptr(), tp_.shape[1]
+            sim = C.c_void_p()
+            _abi.check(lib.mg_sim_create(mnp.ctypes.data, C.byref(sp), h.n, 0, C.byref(sim)), lib)
+            try:
+                _abi.check(lib.mg_sim_bind(sim, C.byref(v)), lib)
+                _abi.check(lib.mg_sim_simulate(sim, torch.cuda.current_stream().cuda_stream), lib)
+                torch.cuda.synchronize()
+            finally:
+                lib.mg_sim_destroy(sim)
+            outs.append({k: getattr(e, k).cpu().numpy() for k in ("root", "dof", "sensors", "dof_force", "rbs")})
+    else:
+        h.act_eff[:] = np.random.default_rng(3).uniform(-1, 1, h.act_eff.shape) * (15.0 if name == "Ant" else 50.0)
+        outs = [vars(_gpu_simulate_dr(lib, spec, sp, h, props=p)[0]) for p in (None, "defaults")]
+    moved = np.abs(outs[0]["dof"][..., 0] - h.dof[..., 0]).max()
+    assert moved > 1e-3, "the step moved nothing"
+    plain, dr = outs
+    n = h.n
+    root_p, root_d = (o["root"].reshape(n, -1, 13)[:, -2 if name == "hand-block" else 0] for o in (plain, dr))
+    checks = [("root pose", root_d[:, 0:7], root_p[:, 0:7], 2e-4, 0), ("root twist", root_d[:, 7:13], root_p[:, 7:13], 2e-3, 2e-3),
+              ("dof pos", dr["dof"][..., 0], plain["dof"][..., 0], 2e-4, 0),
+              ("dof vel", dr["dof"][..., 1], plain["dof"][..., 1], 2e-3, 2e-3),
+              ("dof force", dr["dof_force"], plain["dof_force"], 1e-2 * max(1.0, np.abs(plain["dof_force"]).max()), 0),
+              ("sensors", dr["sensors"], plain["sensors"], 1e-2 * max(1.0, np.abs(plain["sensors"]).max()), 0)]
+    if name == "hand-block":
+        checks.append(("rigid bodies", dr["rbs"], plain["rbs"], 2e-3, 2e-3))
+    test = f"test_default_rows_equal_the_plain_instance[{name}]"
+    outside = {}
+    for k, a, b, atol, rtol in checks:
+        st = PS.record(test, k, a, b, atol=atol, rtol=rtol, differing=int((a != b).sum()))
+        print(f"{test} {k}: max |DR(defaults) - plain| = {st['max']:.3e}, {int((a != b).sum())} of {a.size} elements differ")
+        if PS.env_bad(a, b, atol, rtol).any():
+            outside[k] = st["max"]
+    assert not outside, f"{name}: the DR instance on default rows leaves the one-step bars of the plain instance: {outside}"
 
 
 @pytest.mark.parametrize("task,n", [("Ant", 4096), ("Humanoid", 2048), ("ShadowHand", 1024)])

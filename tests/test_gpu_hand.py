@@ -74,6 +74,7 @@ class DevHandEnv:
         self.force_prob = None if h.force_prob is None else T(h.force_prob)
         self.states = None if h.states is None else T(h.states)
         self.ncf = None if h.ncf is None else T(h.ncf)
+        self.env_props = None if h.env_props is None else T(h.env_props)   # domain-randomized rows, as the oracle's
 
     def views(self):
         v = _abi.StateViews()
@@ -82,6 +83,8 @@ class DevHandEnv:
         v.dof_targets = P(self.targets)
         v.rb_forces, v.rb_force_space = P(self.rb_forces), _abi.MG_LOCAL_SPACE
         v.net_contact_forces = P(self.ncf)
+        if self.env_props is not None:
+            v.env_props, v.env_props_stride = P(self.env_props), self.env_props.shape[1]
         return v
 
     def buffers(self, seed=0, step=0):

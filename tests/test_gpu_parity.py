@@ -127,11 +127,14 @@ class DevEnv:
         self.up = T(h.up)
         self.heading = T(h.heading)
         self.noise = None
+        self.env_props = None if h.env_props is None else T(h.env_props)   # domain-randomized rows, as the oracle's
 
     def views(self):
         v = _abi.StateViews()
         v.root_states, v.dof_state, v.dof_actuation = P(self.root), P(self.dof), P(self.act_eff)
         v.sensors, v.dof_force, v.rigid_body_states = P(self.sensors), P(self.dof_force), None
+        if self.env_props is not None:
+            v.env_props, v.env_props_stride = P(self.env_props), self.env_props.shape[1]
         return v
 
     def buffers(self, seed=0, step=0):

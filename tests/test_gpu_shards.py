@@ -374,3 +374,96 @@ def test_sorted_step_replays_from_a_captured_graph():
     torch.cuda.synchronize()
     for e in (env, twin, lists):
         e.close()
+
+
+# ------------------------------------------------------------------------------------------ with randomization on
+# task.randomize binds env_props, so every launch above turns into its domain-randomized instance (k_env_step<DR> /
+# k_hand_step<DR>), which reads each actor's row by the PERMUTED actor index under a work order, and mg_dr_apply /
+# mg_dr_noise key their draws by env_offset + actor (migym/dr.py).  The two tests below are the work-order and the
+# ragged-shard tests with randomization on: frequency 1 and a 7-step episode, so rows are redrawn inside the run.
+DR_SEED = 20240607   # of the global numpy generator that draws the sim_params attributes (gravity); nothing else seeds it
+
+
+def _dr_rollout(task, n, env_cfg, steps, mode=None, offset=0, acts=None):
+    """`steps` fused steps with task.randomize on: per step (obs, rew, reset, root state, dof state, progress,
+    env_props, the per-actor DR counters) cloned, the scalar DR counters at the end, the actions used, resets seen"""
+    import numpy as np
+    old = os.environ.get("MIGYM_ORDER")
+    if mode is not None:
+        os.environ["MIGYM_ORDER"] = mode
+    try:
+        np.random.seed(DR_SEED)
+        cfg = configs.task_config(task, n, sim_device=DEV)
+        cfg["env_offset"] = offset
+        cfg["env"].update(env_cfg)
+        cfg["env"]["episodeLength"] = 7
+        cfg["task"]["randomize"] = True
+        cfg["task"]["randomization_params"]["frequency"] = 1
+        env = migym.make(seed=17, task=task, num_envs=n, sim_device=DEV, rl_device=DEV, headless=True,
+                         cfg={"task": cfg})
+    finally:
+        if mode is not None:
+            if old is None:
+                del os.environ["MIGYM_ORDER"]
+            else:
+                os.environ["MIGYM_ORDER"] = old
+    assert env.randomize and env.env_props.shape[0] == env.num_actors
+    if acts is None:
+        g = torch.Generator(device=DEV).manual_seed(23)
+        acts = [torch.rand((env.num_actors, env.num_actions), device=DEV, generator=g) * 2.4 - 1.2 for _ in range(steps)]
+    root = env.root_state_tensor if task == "ShadowHand" else env.root_states
+    out = []
+    for a in acts:
+        obs, rew, reset, _ = env.step(a.contiguous())
+        out.append((obs["obs"].clone(), rew.clone(), reset.clone(), root.clone().reshape(env.num_envs, -1),
+                    env.dof_state.clone().reshape(env.num_envs, -1), env.progress_buf.clone(), env.env_props.clone(),
+                    env.randomize_buf_actors.clone()))
+    scalars = (env._dr["calls"], env.last_step, env.last_rand_step, env.frame_count, tuple(env.sim_params.gravity))
+    resets = sum(int(o[2].sum()) for o in out[1:])
+    env.close()
+    return out, scalars, acts, resets
+
+
+DR_NAMES = ("obs", "rew", "reset", "root state", "dof state", "progress", "env_props", "randomize_buf")
+
+
+@pytest.mark.parametrize("mode", ["lists", "sort"])
+@pytest.mark.parametrize("task,n,env_cfg", [("Ant", 301, {}), ("Humanoid", 301, {}),
+                                            ("ShadowHand", 301, {"objectType": "block"})])
+def test_work_order_changes_no_result_with_randomization(task, n, env_cfg, mode):
+    """test_work_order_changes_no_result with task.randomize on: an ordered launch runs slot s on actor order[s], and
+    the domain-randomized step must read THAT actor's env_props row (a row taken by the slot index would pass every
+    test that runs without env_props).  12 steps, ordering every step against never: obs, rew, reset, root and DOF
+    state, progress, the env_props rows and the DR counters bit for bit, with resets (so rows are redrawn) inside."""
+    assert torch.cuda.is_available(), "GPU tests need the MI355X"
+    on, s_on, acts, r_on = _dr_rollout(task, n, env_cfg, 12, mode=mode)
+    off, s_off, _, r_off = _dr_rollout(task, n, env_cfg, 12, mode="off")
+    assert r_on == r_off and r_on > 0
+    assert s_on == s_off, f"{task}: the DR counters differ with the work order on: {s_on} vs {s_off}"
+    first, last = off[0][6], off[-1][6]
+    assert not torch.equal(last[0], last[1]), "every actor has the same row: the test would check nothing"
+    assert not torch.equal(first, last), "no row was redrawn inside the run"
+    for k, (a, b) in enumerate(zip(on, off)):
+        for name, x, y in zip(DR_NAMES, a, b):
+            assert torch.equal(x, y), f"{task} {env_cfg} step {k}: {name} differ with the work order on"
+
+
+@pytest.mark.parametrize("task,n,cuts,env_cfg", [("Ant", 301, (75, 226), {}),
+                                                 ("ShadowHand", 67, (7, 30), {"objectType": "block"})])
+def test_ragged_shards_equal_slices_with_randomization(task, n, cuts, env_cfg):
+    """test_ragged_shards_equal_slices_of_one_rollout with task.randomize on: a shard made with its env_offset draws
+    the rows, the noise and the resets of its slice of the full batch (migym/dr.py offsets mg_dr_apply's and
+    mg_dr_noise's keys), so over 8 steps with re-randomization it is that slice bit for bit, env_props rows and DR
+    counters included."""
+    assert torch.cuda.is_available(), "GPU tests need the MI355X"
+    steps = 8
+    full, s_full, acts, resets = _dr_rollout(task, n, env_cfg, steps)
+    assert resets > 0 and all(torch.isfinite(o[0]).all() for o in full)
+    assert not torch.equal(full[0][6], full[-1][6]), "no row was redrawn inside the run"
+    edges = (0,) + tuple(cuts) + (n,)
+    for lo, hi in zip(edges[:-1], edges[1:]):
+        sh, s_sh, _, _ = _dr_rollout(task, hi - lo, env_cfg, steps, offset=lo, acts=[a[lo:hi] for a in acts])
+        assert s_sh == s_full, f"{task} envs [{lo}, {hi}): the DR counters differ: {s_sh} vs {s_full}"
+        for k, (a, b) in enumerate(zip(sh, full)):
+            for name, x, y in zip(DR_NAMES, a, b):
+                assert torch.equal(x, y[lo:hi]), f"{task} envs [{lo}, {hi}) step {k}: {name} differ from the slice"
