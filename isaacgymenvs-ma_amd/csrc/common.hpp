@@ -11,6 +11,11 @@
 // LDS then holds twelve waves per CU.  Its ABA slots are per tree level (kCompactLevelSlots nodes at one depth at most),
 // which the dispatcher checks against the model (dispatch.hpp MG_FITS).  MIGYM_LAYOUT=classic turns it off at run time
 constexpr int kCompactLevelSlots = 8;
+// The 16-lane compact teams add the root's children up over the team's lanes (Team::aba()): the root's
+// own 27 values go to the first slot its nch children leave free and each lane sums two entries.  That slot
+// (ModelTile::lvs[0]), or 0 where the root has fewer than two children or its level leaves no slot free: such models
+// take the root's own serial sum.
+constexpr int mg_root_sum_slot(int nch) { return nch >= 2 && nch < kCompactLevelSlots ? nch : 0; }
 constexpr bool mg_compact_layout(int T, int MN, int OBJ) {
   return (T == 16 || T == 32) && OBJ == 0 && MN <= 32;
 }

@@ -58,7 +58,8 @@ struct alignas(16) ModelTile {
   int parent[MN], jtype[MN], limited[MN];
   unsigned long long children[MN];
   unsigned long long anc[MN];   // ancestor mask of each node (itself and the root included)
-  int lvs[MN];                  // the node's index among the nodes of its depth (compact layout's ABA slot)
+  int lvs[MN];                  // the node's index among the nodes of its depth (compact layout's ABA slot);
+                                // [0]: the slot of the root's team-wide child sum (0: none)
   float nf[MN][33];   // 0-8 Rr0, 9-11 t, 12-14 axis, 15-17 com, 18-23 inertia, 24 mass, 25 arm, 26 damp,
                       // 27 stiff, 28 lower, 29 upper, 30 drive kp, 31 effort limit, 32 frictionloss
   int gtype[MG], gnode[MG], gbody[MG], gfil[MG];
@@ -103,7 +104,8 @@ __host__ __device__ void build_tile(ModelTile<MN, MG, MP, HV>* t, const mg_model
       for (int j = k; j > 0; j = m->parent[j]) dk++;
       lv += dk == di ? 1 : 0;
     }
-    t->lvs[i] = i > 0 ? lv : 0;
+    // (the root has no slot of its own: its entry is the slot of its team-wide child sum, common.hpp mg_root_sum_slot)
+    t->lvs[i] = i > 0 ? lv : mg_root_sum_slot(__builtin_popcountll(ch));
     float* f = t->nf[i];
     const M3 R0 = quat_to_mat(m->r0[i][0], m->r0[i][1], m->r0[i][2], m->r0[i][3]);
     for (int a = 0; a < 3; a++)
@@ -477,6 +479,7 @@ struct TeamLDSC {
   __device__ __forceinline__ Stage& st() { return post.st; }
   __device__ __forceinline__ float* qvsc() { return &slots[0][0]; }
   __device__ __forceinline__ float* slot(int, int lv) { return slots[lv]; }  // by the node's slot in its level
+  __device__ __forceinline__ float* level_slot(int lv) { return slots[lv]; }  // a level's slot by its index
   __device__ __forceinline__ float* acc(int node) { return aba.acc[node]; }
   __device__ __forceinline__ float* aproot() { return aba.proot; }
   __device__ __forceinline__ float* l0() { return aba.L0; }
@@ -900,6 +903,8 @@ struct Team : TeamXf<XF> {
   static constexpr int MR = L::MR;
   // the hardware sine / cosine for the 16-lane teams (Ant, MA-Ant), poly_sincos elsewhere (device_math.hpp psincos)
   static constexpr bool kHwTrig = T == 16 && OBJ == 0;
+  // the root's child sum over the team's lanes (aba()): the 16-lane compact teams
+  static constexpr bool kRootSum = L::kCompact && T == 16;
   L* s;
   const MT* mt;
   const mg_model* m;
@@ -1226,7 +1231,44 @@ struct Team : TeamXf<XF> {
         s->U[node][3] = U.l.x; s->U[node][4] = U.l.y; s->U[node][5] = U.l.z;
         s->Dinv[node] = Dinv;
       }
+      // 16-lane compact teams: the root's child sum over the team's lanes.  Lane 0 alone would read and add 27 floats
+      // per child while the team waits; instead it publishes its own 27 (IA, pA in the slots' order) to the slot its
+      // children leave free, lane l adds the children's entries l and l + 16 onto them in the children's order --
+      // level 1's slots in turn are the root's children by rising node, the order of the serial sum below, so every
+      // entry is ((own + c1) + c2) + ... as there and has its bits -- and lane 0 reads the sums back.  Lanes 11 .. 15
+      // repeat entry 26 (the same value to the same word).
+      const int rsl = (kRootSum && lev == 1 && freeb) ? mt->lvs[0] : 0;
+      if constexpr (kRootSum) {
+        if (rsl > 0 && node == 0) {
+          float* rs = s->level_slot(rsl);
+          for (int k = 0; k < 6; k++) { rs[k] = IA.a[k]; rs[15 + k] = IA.c[k]; }
+          for (int k = 0; k < 9; k++) rs[6 + k] = IA.b[k];
+          rs[21] = pA.a.x; rs[22] = pA.a.y; rs[23] = pA.a.z;
+          rs[24] = pA.l.x; rs[25] = pA.l.y; rs[26] = pA.l.z;
+        }
+      }
       wsync();
+      if constexpr (kRootSum) {
+        if (rsl > 0) {
+          float* rs = s->level_slot(rsl);
+          const int e0 = tl, e1 = tl + 16 < 27 ? tl + 16 : 26;
+          float v0 = rs[e0], v1 = rs[e1];
+          for (int j = 0; j < rsl; j++) {
+            const float* sl = s->level_slot(j);
+            v0 += sl[e0];
+            v1 += sl[e1];
+          }
+          rs[e0] = v0;
+          rs[e1] = v1;
+          wsync();
+          if (node == 0) {
+            for (int q = 0; q < 6; q++) { IA.a[q] = rs[q]; IA.c[q] = rs[15 + q]; }
+            for (int q = 0; q < 9; q++) IA.b[q] = rs[6 + q];
+            pA = sv(v3(rs[21], rs[22], rs[23]), v3(rs[24], rs[25], rs[26]));
+          }
+          continue;
+        }
+      }
       if (node >= 0 && depth == lev - 1) {
         unsigned long long ch = mt->children[node];
         while (ch) {
