@@ -15,6 +15,10 @@
  *   mg_sim_set_link_forces
  *                        gym.apply_rigid_body_force_tensors on articulation links
  *                                                   (tasks/quadcopter.py:330)
+ *   mg_sim_set_heightfield
+ *                        gym.add_triangle_mesh of a terrain_utils heightfield
+ *                                                   (tasks/anymal_terrain.py:159-176), as facets of the grid
+ *   mg_height_scan       AnymalTerrain.get_heights  (tasks/anymal_terrain.py:515-538)
  *   mg_set_indexed       gym.set_actor_root_state_tensor_indexed /
  *                        gym.set_dof_state_tensor_indexed
  *                                                   (tasks/ant.py:265-271, cartpole.py:153-155)
@@ -471,6 +475,35 @@ int mg_sim_simulate(mg_sim* sim, void* stream);
  * bound, the compact layout pinned, or more bodies than the instance has nodes; mg_env_step and mg_env_step_replay
  * fail while it is on.  enable == 0 (the default): exactly the behaviour without this call. */
 int mg_sim_set_link_forces(mg_sim* sim, int32_t enable);
+/* Heightfield terrain (the ground of the reference's terrain tasks, tasks/anymal_terrain.py): fp32
+ * heights in metres on a grid of square cells, heights[i * ny + j] at world (x0 + i dx, y0 + j dx) -- the index order of
+ * the reference's height_samples[px, py].  env_origins: NULL, or (N, 3) fp32, actor a's local point (x, y, z) sitting
+ * at world (x + ox, y + oy, z + oz).  hmax: an upper bound of heights, supplied by the caller (the ground-contact cull
+ * relies on it).  heights and env_origins are device pointers, kept and not copied: the caller keeps them alive and may
+ * rewrite their contents between launches. */
+typedef struct mg_heightfield {
+  const float* heights;
+  int32_t nx, ny;           /* >= 2 each */
+  float dx, x0, y0, hmax;
+  const float* env_origins;
+} mg_heightfield;
+size_t mg_heightfield_sizeof(void);
+/* hf != NULL: every later mg_sim_simulate and mg_debug_contacts takes each ground candidate against the triangular
+ * facet of the field under it instead of the plane z = 0: the point is clamped to the grid rectangle, the cell's
+ * facets are split by the diagonal from (i, j) to (i + 1, j + 1), the contact has the facet's normal n, the gap
+ * (z - h) n.z - r and the point e - r n (DESIGN.md §15 has the formulas and the limits: a candidate sees only the facet
+ * directly under it).  The launch then takes instances of its own, in the classic team layout at every batch size, and
+ * fails (nothing launched or written) on a model with a free object, with env_props bound, with the compact layout
+ * pinned, or with link forces on; mg_env_step and mg_env_step_replay fail while a field is set.  Fails on a NULL
+ * table, nx or ny < 2, or a dx that is not finite and positive.  hf == NULL (the default): the plane, exactly the
+ * behaviour without this call. */
+int mg_sim_set_heightfield(mg_sim* sim, const mg_heightfield* hf);
+/* The terrain height under a pattern of points that turns with each actor's yaw (get_heights, tasks/anymal_terrain.py:
+ * 515-538): points (P, 2) fp32 on the device, out (N, P).  Per actor and point: the point is rotated by the yaw of the
+ * bound root quaternion (quat_apply_yaw: x and y zeroed, normalised), the root's x, y and the env origin are added,
+ * px = trunc((X - x0) / dx) clipped to [0, nx - 2], py likewise, out = min(H[px][py], H[px + 1][py + 1]) - oz.
+ * Asynchronous on `stream`.  Fails without a field set. */
+int mg_height_scan(mg_sim* sim, const float* points, int32_t num_points, float* out, void* stream);
 int mg_sim_destroy(mg_sim* sim);
 
 /* Scatter rows of `src` (same layout as the bound buffer) into the bound

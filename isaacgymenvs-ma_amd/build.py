@@ -6,6 +6,9 @@
     hipcc ... -c csrc/inst.hip -DMG_INST=i -DMG_CONTACTS_TU       (the instance's contact read-out, tests only)
     hipcc ... -c csrc/inst.hip -DMG_INST=i -DMG_LINKFORCE_TU      (k_simulate with link forces: the objectless
                                                                     instances in the classic layout)
+    hipcc ... -c csrc/inst.hip -DMG_INST=i -DMG_HEIGHTFIELD_TU    (k_simulate on heightfield terrain and its contact
+                                                                    read-out: the same instances)
+    hipcc -O3 --offload-arch=gfx950 -c csrc/height_scan.hip       (mg_height_scan's kernel)
     hipcc -shared *.o -> migym/_lib/libmigym.so
 
 The objects compile in parallel (one process per translation unit, at most MIGYM_JOBS / os.cpu_count()).
@@ -23,6 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SRC = os.path.join(CSRC, "migym.hip")
 INST = os.path.join(CSRC, "inst.hip")
+SCAN = os.path.join(CSRC, "height_scan.hip")
 OUT = os.path.join(HERE, "migym", "_lib", "libmigym.so")
 OUT_TIMING = os.path.join(HERE, "migym", "_lib", "libmigym_timing.so")
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "migym.h")]
@@ -47,7 +51,7 @@ def needs_build(out=OUT):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(p) > t for p in [SRC, INST, __file__] + HEADERS)
+    return any(os.path.getmtime(p) > t for p in [SRC, INST, SCAN, __file__] + HEADERS)
 
 
 def _run_parallel(cmds, verbose):
@@ -117,6 +121,17 @@ def build(force=False, verbose=False, timing=False, variant=None, defines=(), ex
         cmds.append([hipcc] + flags + [f"-DMG_INST={i}", "-mllvm", "-disable-machine-licm", "-mllvm", "-enable-ipra=false",
                                        "-DMG_LINKFORCE_TU", "-c", "-o", o, INST])
         objs.append(o)
+    # ... and last the heightfield variants (-DMG_HEIGHTFIELD_TU, mg_sim_set_heightfield): k_simulate_hf and the contact
+    # read-out that goes with it, for the same instances
+    for i in linkforce_instances():
+        o = os.path.join(objdir, f"heightfield{i}.o")
+        cmds.append([hipcc] + flags + [f"-DMG_INST={i}", "-mllvm", "-disable-machine-licm", "-mllvm", "-enable-ipra=false",
+                                       "-DMG_HEIGHTFIELD_TU", "-c", "-o", o, INST])
+        objs.append(o)
+    # ... and mg_height_scan's kernel (height_scan.hip)
+    o = os.path.join(objdir, "height_scan.o")
+    cmds.append([hipcc] + flags + ["-c", "-o", o, SCAN])
+    objs.append(o)
     _run_parallel(cmds, verbose)
     subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out + ".tmp"] + objs)
     sys.path.insert(0, HERE)

@@ -63,6 +63,10 @@ struct mg_sim {
   mg_dynamics_views dyn;
   // mg_sim_set_link_forces: mg_sim_simulate applies every articulation row of views.rb_forces (k_simulate_xf)
   bool link_forces;
+  // mg_sim_set_heightfield: mg_sim_simulate and mg_debug_contacts take the ground from this field (k_simulate_hf,
+  // k_contacts_hf); the pointers are the caller's
+  bool has_hf;
+  mg_heightfield hf;
 };
 // layout_n under MIGYM_LAYOUT=compact: a batch past every threshold
 constexpr long kLayoutCompact = 1L << 40;
@@ -98,4 +102,6 @@ namespace mgi {
 constexpr int kBlock = 64;
 // sets mg_last_error() (thread-local, defined in migym.hip) and returns `code`
 int fail(int code, const std::string& msg);
+// mg_height_scan's launch (height_scan.hip): out (n, P) from the sim's bound root_states and its heightfield
+void launch_height_scan(hipStream_t s, const mg_sim* sim, const float* points, int P, float* out);
 }  // namespace mgi

@@ -66,6 +66,35 @@ struct SimulateXF {
       return RunSimulateXF<T, MN, MC, MG, MP>::run(s, sim);
   }
 };
+// gym.simulate on heightfield terrain (k_simulate_hf; mg_sim_set_heightfield) and its contact read-out (k_contacts_hf):
+// the objectless capacities in the classic layout, in translation units of their own (inst.hip -DMG_HEIGHTFIELD_TU)
+template <int T, int MN, int MC, int MG, int MP>
+struct RunSimulateHF {
+  static int run(hipStream_t s, const mg_sim* sim);
+};
+template <int T, int MN, int MC, int MG, int MP>
+struct RunContactsHF {
+  static int run(hipStream_t s, const mg_sim* sim, float* out, int32_t* count, int32_t cap);
+};
+// ... as dispatch functors: the instances they have none for refuse
+template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY>
+struct SimulateHF {
+  static int run(hipStream_t s, const mg_sim* sim) {
+    if constexpr (OBJ != 0 || LAY != 0)
+      return fail(MG_EINVAL, "mg_sim_simulate: a heightfield has no object / hand instance and none in the compact layout");
+    else
+      return RunSimulateHF<T, MN, MC, MG, MP>::run(s, sim);
+  }
+};
+template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY>
+struct ContactsHF {
+  static int run(hipStream_t s, const mg_sim* sim, float* out, int32_t* count, int32_t cap) {
+    if constexpr (OBJ != 0 || LAY != 0)
+      return fail(MG_EINVAL, "mg_debug_contacts: a heightfield has no object / hand instance and none in the compact layout");
+    else
+      return RunContactsHF<T, MN, MC, MG, MP>::run(s, sim, out, count, cap);
+  }
+};
 // phase-timing build: publish the per-wave accumulator buffer to instance I's code object
 template <int I>
 int phase_buf_publish(unsigned long long* buf);

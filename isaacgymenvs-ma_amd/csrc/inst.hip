@@ -3,6 +3,8 @@
 // With -DMG_CONTACTS_TU the unit holds the instance's contact read-out alone (k_contacts, mg_debug_contacts: tests
 // only) -- a code object of its own, so that the shipped instances' code objects are what they are without it.
 // With -DMG_LINKFORCE_TU it holds the instance's k_simulate with link forces alone (k_simulate_xf), likewise.
+// With -DMG_HEIGHTFIELD_TU it holds the instance's k_simulate on heightfield terrain and that kernel's contact read-out
+// alone (k_simulate_hf, k_contacts_hf), likewise.
 #include "step_kernels.hpp"
 
 #ifndef MG_INST
@@ -15,6 +17,10 @@ constexpr InstDesc kI = kInst[MG_INST];
 #if defined(MG_LINKFORCE_TU)
 static_assert(kI.OBJ == 0 && kI.LAY == 0, "link forces: the objectless instances in the classic layout (build.py)");
 template struct RunSimulateXF<kI.T, kI.MN, kI.MC, kI.MG, kI.MP>;
+#elif defined(MG_HEIGHTFIELD_TU)
+static_assert(kI.OBJ == 0 && kI.LAY == 0, "heightfield: the objectless instances in the classic layout (build.py)");
+template struct RunSimulateHF<kI.T, kI.MN, kI.MC, kI.MG, kI.MP>;
+template struct RunContactsHF<kI.T, kI.MN, kI.MC, kI.MG, kI.MP>;
 #elif defined(MG_CONTACTS_TU)
 template struct RunContacts<kI.T, kI.MN, kI.MC, kI.MG, kI.MP, kI.OBJ, kI.LAY>;
 #else

@@ -3,6 +3,7 @@
 // asynchronous on the caller's stream; no entry point synchronises.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
@@ -586,6 +587,8 @@ int mg_sim_create(const mg_model* model, const mg_sim_params* params, int32_t nu
   s->device = device;
   s->bound = false;
   s->link_forces = false;
+  s->has_hf = false;
+  s->hf = mg_heightfield{};
   if (hipMalloc(&s->d_model, sizeof(mg_model)) != hipSuccess) {
     delete s;
     return fail(MG_ENOMEM, "mg_sim_create: hipMalloc(model) failed");
@@ -715,8 +718,29 @@ int mg_sim_bind(mg_sim* sim, const mg_state_views* views) {
   return MG_OK;
 }
 
+// what a launch on the sim's heightfield refuses (nothing launched or written)
+static int heightfield_ok(const mg_sim* sim, const char* who) {
+  if (sim->host_model.obj_type)
+    return fail(MG_EINVAL, std::string(who) + ": a heightfield has no instance for a model with a free object");
+  if (sim->views.env_props)
+    return fail(MG_EINVAL, std::string(who) + ": a heightfield has no domain-randomized instance (env_props is bound)");
+  if (sim->layout_n >= kLayoutCompact)
+    return fail(MG_EINVAL, std::string(who) + ": a heightfield has no instance in the compact layout (MIGYM_LAYOUT=compact)");
+  if (sim->link_forces)
+    return fail(MG_EINVAL, std::string(who) + ": a heightfield has no instance with link forces (mg_sim_set_link_forces is on)");
+  return MG_OK;
+}
+
 int mg_sim_simulate(mg_sim* sim, void* stream) {
   if (!sim || !sim->bound) return fail(MG_EINVAL, "mg_sim_simulate: sim not bound");
+  if (sim->has_hf) {
+    // heightfield terrain (mg_sim_set_heightfield): the classic layout's own instances at every batch size
+    if (int rc = heightfield_ok(sim, "mg_sim_simulate")) return rc;
+    int rc = mgi::dispatch<mgi::SimulateHF>(sim->host_model, sim->params.max_contacts, 0L, (hipStream_t)stream,
+                                            (const mg_sim*)sim);
+    if (rc) return rc;
+    return check_launch("mg_sim_simulate");
+  }
   if (sim->link_forces) {
     // link forces (mg_sim_set_link_forces): the classic layout's own instances at every batch size
     if (!sim->views.rb_forces) return fail(MG_EINVAL, "mg_sim_simulate: link forces are on and no rb_forces tensor is bound");
@@ -735,6 +759,40 @@ int mg_sim_simulate(mg_sim* sim, void* stream) {
   return check_launch("mg_sim_simulate");
 }
 
+// the field's own checks (they need no sim, and come first)
+static int heightfield_args_ok(const mg_heightfield* hf) {
+  if (!hf->heights) return fail(MG_EINVAL, "mg_sim_set_heightfield: heights is NULL");
+  if (hf->nx < 2 || hf->ny < 2) return fail(MG_EINVAL, "mg_sim_set_heightfield: nx and ny must be at least 2");
+  if (!std::isfinite(hf->dx) || !(hf->dx > 0.0f))
+    return fail(MG_EINVAL, "mg_sim_set_heightfield: dx must be finite and positive");
+  if (!std::isfinite(hf->x0) || !std::isfinite(hf->y0) || !std::isfinite(hf->hmax))
+    return fail(MG_EINVAL, "mg_sim_set_heightfield: x0, y0 and hmax must be finite");
+  return MG_OK;
+}
+
+int mg_sim_set_heightfield(mg_sim* sim, const mg_heightfield* hf) {
+  if (hf)
+    if (int rc = heightfield_args_ok(hf)) return rc;
+  if (!sim) return fail(MG_EINVAL, "mg_sim_set_heightfield: bad arguments (sim is NULL)");
+  sim->has_hf = hf != nullptr;   // NULL: back to the plane z = 0
+  sim->hf = hf ? *hf : mg_heightfield{};
+  return MG_OK;
+}
+
+size_t mg_heightfield_sizeof(void) { return sizeof(mg_heightfield); }
+
+int mg_height_scan(mg_sim* sim, const float* points, int32_t num_points, float* out, void* stream) {
+  if (!sim || !sim->bound) return fail(MG_EINVAL, "mg_height_scan: sim not bound");
+  if (!sim->has_hf) return fail(MG_EINVAL, "mg_height_scan: no heightfield is set (mg_sim_set_heightfield)");
+  if (!points || !out || num_points < 0) return fail(MG_EINVAL, "mg_height_scan: bad arguments");
+  if (sim->host_model.obj_type)
+    return fail(MG_EINVAL, "mg_height_scan: a heightfield has no instance for a model with a free object");
+  if (!sim->views.root_states) return fail(MG_EINVAL, "mg_height_scan: needs root_states");
+  if (sim->n == 0 || num_points == 0) return MG_OK;
+  mgi::launch_height_scan((hipStream_t)stream, sim, points, num_points, out);
+  return check_launch("mg_height_scan");
+}
+
 int mg_sim_set_link_forces(mg_sim* sim, int32_t enable) {
   if (!sim) return fail(MG_EINVAL, "mg_sim_set_link_forces: bad arguments");
   sim->link_forces = enable != 0;
@@ -748,6 +806,13 @@ int mg_debug_contacts(mg_sim* sim, float* out, int32_t* count, int32_t cap, void
   if (!out || !count || cap < 0) return fail(MG_EINVAL, "mg_debug_contacts: bad arguments");
   if (sim->views.env_props || sim->params.solver_type != MG_SOLVER_PGS)
     return fail(MG_EINVAL, "mg_debug_contacts: no read-out of the domain-randomized or TGS instances");
+  if (sim->has_hf) {
+    if (int rc = heightfield_ok(sim, "mg_debug_contacts")) return rc;
+    int rc = mgi::dispatch<mgi::ContactsHF>(sim->host_model, sim->params.max_contacts, 0L, (hipStream_t)stream,
+                                            (const mg_sim*)sim, out, count, cap);
+    if (rc) return rc;
+    return check_launch("mg_debug_contacts");
+  }
   int rc = mgi::dispatch<mgi::RunContacts>(sim->host_model, sim->params.max_contacts, sim->layout_n, (hipStream_t)stream,
                                            (const mg_sim*)sim, out, count, cap);
   if (rc) return rc;
@@ -1121,6 +1186,9 @@ static int env_step(mg_sim* sim, const mg_task_params* tp, const mg_task_buffers
   if (!sim || !sim->bound || !tp || !tb || !tb->actions || !tb->obs || !tb->rew || !tb->reset || !tb->progress ||
       !tb->timeout)
     return fail(MG_EINVAL, "mg_env_step: bad arguments");
+  if (sim->has_hf)
+    return fail(MG_EINVAL, rp ? "mg_env_step_replay: the fused step has no heightfield instance (mg_sim_set_heightfield is set)"
+                              : "mg_env_step: the fused step has no heightfield instance (mg_sim_set_heightfield is set)");
   if (sim->link_forces)
     return fail(MG_EINVAL, rp ? "mg_env_step_replay: the fused step applies no link forces (mg_sim_set_link_forces is on)"
                               : "mg_env_step: the fused step applies no link forces (mg_sim_set_link_forces is on)");

@@ -265,6 +265,100 @@ __global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>::kT
   }
 }
 
+// gym.simulate on heightfield terrain (mg_sim_set_heightfield): k_simulate's objectless, non-DR instance in the classic
+// layout, with the ground contacts of Team::collide() taken against the facet of the field under each candidate (HF;
+// DESIGN.md §15).  The descriptor is a kernel argument (wave-uniform); the table stays in global memory and each
+// candidate that passes the cull loads its cell's four heights; the actor's env origin is read once.
+template <int T, int MN, int MC, int MG, int MP, bool TGS = false>
+__global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, 0, false, 0>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, 0, false, 0>::kWPE))) void k_simulate_hf(
+    const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n, mg::HfDesc hf,
+    const float* __restrict__ env_origins) {
+  using SH = Shape<T, MN, MC, MG, MP, 0, false, 0>;
+  constexpr int E = SH::E;
+  __shared__ mg::BankSlot<mg::TeamLDSOf<T, MN, MC, 0, MG, MP, 0>, T> lds[E];
+  __shared__ typename mg::Team<T, MN, MC, MG, MP, 0>::MT tile;
+  mg::copy_tile(&tile, static_cast<const typename mg::Team<T, MN, MC, MG, MP, 0>::MT*>(timg));
+  __syncthreads();
+  const int team = threadIdx.x / T;
+  const int a = blockIdx.x * E + team;
+  const bool valid = a < n;
+  const int ac = valid ? a : n - 1;
+  const int nd = m->num_dofs, ns = m->num_sensors, nb = m->num_bodies;
+  mg::Team<T, MN, MC, MG, MP, 0, TGS, 0, false, true> t;
+  t.init(&lds[team].v, &tile, m, &p);
+  t.bind_hf(hf, env_origins ? env_origins + (size_t)3 * ac : nullptr);
+  float* root = v.root_states + (size_t)13 * ac;
+  t.load(root, v.dof_state + (size_t)2 * nd * ac, v.dof_actuation ? v.dof_actuation + (size_t)nd * ac : nullptr, nullptr,
+         v.dof_targets ? v.dof_targets + (size_t)nd * ac : nullptr);
+  for (int st = 0; st < p.substeps; st++) t.substep();
+  t.outputs(lds[team].v.st().sens, lds[team].v.st().dforce,
+            (valid && v.net_contact_forces) ? v.net_contact_forces + (size_t)3 * nb * a : nullptr);
+  t.stage_state();
+  mg::wsync();
+  if (valid) {
+    auto& L = lds[team].v;
+    if (!m->fixed_base)
+      for (int k = t.tl; k < 13; k += T) root[k] = L.st().root[k];
+    for (int k = t.tl; k < 2 * nd; k += T) v.dof_state[(size_t)2 * nd * a + k] = L.st().dof[k];
+    if (v.sensors)
+      for (int k = t.tl; k < 6 * ns; k += T) v.sensors[(size_t)6 * ns * a + k] = L.st().sens[k];
+    if (v.dof_force)
+      for (int k = t.tl; k < nd; k += T) v.dof_force[(size_t)nd * a + k] = L.st().dforce[k];
+    if (v.rigid_body_states) {
+      float* rb = v.rigid_body_states + (size_t)13 * nb * a;
+      for (int b = t.tl; b < nb; b += T) t.body_state(b, rb + 13 * b);
+    }
+  }
+}
+
+// mg_debug_contacts while a heightfield is set (tests only): k_contacts below for k_simulate_hf -- the same call
+// sequence (change them together), rows and launch shape
+template <int T, int MN, int MC, int MG, int MP>
+__global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, 0, false, 0>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, 0, false, 0>::kWPE))) void k_contacts_hf(
+    const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n, mg::HfDesc hf,
+    const float* __restrict__ env_origins, float* __restrict__ out, int* __restrict__ count, int cap) {
+  using SH = Shape<T, MN, MC, MG, MP, 0, false, 0>;
+  constexpr int E = SH::E;
+  __shared__ mg::BankSlot<mg::TeamLDSOf<T, MN, MC, 0, MG, MP, 0>, T> lds[E];
+  __shared__ typename mg::Team<T, MN, MC, MG, MP, 0>::MT tile;
+  mg::copy_tile(&tile, static_cast<const typename mg::Team<T, MN, MC, MG, MP, 0>::MT*>(timg));
+  __syncthreads();
+  const int team = threadIdx.x / T;
+  const int a = blockIdx.x * E + team;
+  const bool valid = a < n;
+  const int ac = valid ? a : n - 1;
+  const int nd = m->num_dofs;
+  mg::Team<T, MN, MC, MG, MP, 0, false, 0, false, true> t;
+  t.init(&lds[team].v, &tile, m, &p);
+  t.bind_hf(hf, env_origins ? env_origins + (size_t)3 * ac : nullptr);
+  float* root = v.root_states + (size_t)13 * ac;
+  t.load(root, v.dof_state + (size_t)2 * nd * ac, v.dof_actuation ? v.dof_actuation + (size_t)nd * ac : nullptr, nullptr,
+         v.dof_targets ? v.dof_targets + (size_t)nd * ac : nullptr);
+  t.hull_stage();
+  t.fk();
+  t.set_axis();
+  t.aba();
+  t.obj_free();
+  t.collide();  // ends with a wave sync: s->ncon and the list are visible to the team
+  if (valid) {
+    auto& L = lds[team].v;
+    const int nc = L.ncon;
+    if (t.tl == 0) count[a] = nc;
+    for (int c = t.tl; c < nc && c < cap; c += T) {
+      float* o = out + ((size_t)a * cap + c) * 11;
+      o[0] = (float)t.cside(c, 0);
+      o[1] = (float)t.cside(c, 2);
+      o[2] = (float)t.cside(c, 1);
+      o[3] = (float)t.cside(c, 3);
+      for (int k = 0; k < 3; k++) {
+        o[4 + k] = L.cp[c][k];
+        o[7 + k] = L.cn[c][k];
+      }
+      o[10] = L.gap(c);
+    }
+  }
+}
+
 // mg_debug_contacts (tests only): the contact list of the first substep of k_simulate, per actor.  The same Team,
 // LDS layout, model tile, init / load and launch shape as k_simulate above, and the front half of
 // Team::substep() up to collide() -- THE CALL SEQUENCE BELOW REPEATS Team::substep()'s (team_physics.hpp): change
@@ -1157,6 +1251,36 @@ int RunSimulateXF<T, MN, MC, MG, MP>::run(hipStream_t s, const mg_sim* sim) {
   else
     launch<SH>(k_simulate_xf<T, MN, MC, MG, MP, false>, s, sim->n, sim->d_model, (const void*)sim->d_tile, sim->params,
                sim->views, sim->n);
+  return MG_OK;
+}
+
+// the kernels' descriptor of the field the sim has set
+static mg::HfDesc hf_desc(const mg_heightfield& f) {
+  return mg::HfDesc{f.heights, f.nx, f.ny, f.dx, f.x0, f.y0, f.x0 + (float)(f.nx - 1) * f.dx, f.y0 + (float)(f.ny - 1) * f.dx,
+                    f.hmax};
+}
+
+template <int T, int MN, int MC, int MG, int MP>
+int RunSimulateHF<T, MN, MC, MG, MP>::run(hipStream_t s, const mg_sim* sim) {
+  if (!sim->d_tile) return fail(MG_ECAPACITY, "mg_sim_simulate: no model tile (model exceeds every kernel instance)");
+  using SH = Shape<T, MN, MC, MG, MP, 0, false, 0>;
+  if (sim->params.solver_type == MG_SOLVER_TGS)
+    launch<SH>(k_simulate_hf<T, MN, MC, MG, MP, true>, s, sim->n, sim->d_model, (const void*)sim->d_tile, sim->params,
+               sim->views, sim->n, hf_desc(sim->hf), sim->hf.env_origins);
+  else
+    launch<SH>(k_simulate_hf<T, MN, MC, MG, MP, false>, s, sim->n, sim->d_model, (const void*)sim->d_tile, sim->params,
+               sim->views, sim->n, hf_desc(sim->hf), sim->hf.env_origins);
+  return MG_OK;
+}
+
+template <int T, int MN, int MC, int MG, int MP>
+int RunContactsHF<T, MN, MC, MG, MP>::run(hipStream_t s, const mg_sim* sim, float* out, int32_t* count, int32_t cap) {
+  if (!sim->d_tile) return fail(MG_ECAPACITY, "mg_debug_contacts: no model tile (model exceeds every kernel instance)");
+  const int kept = sim->params.max_contacts < MC ? sim->params.max_contacts : MC;
+  if (cap < kept) return fail(MG_EINVAL, "mg_debug_contacts: cap is below the kernel's contact count");
+  launch<Shape<T, MN, MC, MG, MP, 0, false, 0>>(k_contacts_hf<T, MN, MC, MG, MP>, s, sim->n, sim->d_model,
+                                                (const void*)sim->d_tile, sim->params, sim->views, sim->n, hf_desc(sim->hf),
+                                                sim->hf.env_origins, out, count, (int)cap);
   return MG_OK;
 }
 

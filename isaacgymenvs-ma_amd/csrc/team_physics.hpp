@@ -896,8 +896,52 @@ struct TeamXf<true> {
   unsigned long long xfm;  // the bodies of this lane's node whose row is not zero
   bool xfl;
 };
-template <int T, int MN, int MC, int MG, int MP, int OBJ = 0, bool TGS = false, int LAY = 0, bool XF = false>
-struct Team : TeamXf<XF> {
+// HF: heightfield terrain (mg_sim_set_heightfield; bind_hf() below, the ground contacts of collide()) -- instances of
+// their own once more, their state an empty base otherwise
+template <bool HF>
+struct TeamHf {};
+// the field's descriptor (wave-uniform: kernel arguments) and this lane's actor's origin in it
+struct HfDesc {
+  const float* tab;    // H[nx][ny], metres, H[i * ny + j] at world (x0 + i dx, y0 + j dx)
+  int nx, ny;
+  float dx, x0, y0;
+  float x1, y1;        // the grid rectangle's far corner: x0 + (nx - 1) dx, y0 + (ny - 1) dx
+  float hmax;          // an upper bound of H
+};
+template <>
+struct TeamHf<true> {
+  HfDesc hf;
+  float hox, hoy, hoz;  // env origin of the lane's actor: an actor-local (x, y, z) is at world (x + ox, y + oy, z + oz)
+  float hcull;          // hmax - oz: no local height is above it
+};
+// the facet under the world point (X, Y): its height and unit normal.  The point is clamped to the
+// grid rectangle first, so the four loads stay inside the table whatever (X, Y) is -- a NaN included: fminf / fmaxf
+// return their other operand, and the cell index is clamped again as an integer
+__device__ __forceinline__ void hf_facet(const HfDesc& f, float X, float Y, float* h, V3* n) {
+  X = fminf(fmaxf(X, f.x0), f.x1);
+  Y = fminf(fmaxf(Y, f.y0), f.y1);
+  const float u = (X - f.x0) / f.dx, v = (Y - f.y0) / f.dx;
+  int i = (int)floorf(u), j = (int)floorf(v);
+  i = i < 0 ? 0 : (i > f.nx - 2 ? f.nx - 2 : i);
+  j = j < 0 ? 0 : (j > f.ny - 2 ? f.ny - 2 : j);
+  const float fu = u - (float)i, fv = v - (float)j;
+  const float* c = f.tab + (size_t)i * f.ny + j;
+  const float h00 = c[0], h01 = c[1], h10 = c[f.ny], h11 = c[f.ny + 1];
+  float gx, gy;
+  if (fu >= fv) {
+    *h = h00 + (h10 - h00) * fu + (h11 - h10) * fv;
+    gx = (h10 - h00) / f.dx;
+    gy = (h11 - h10) / f.dx;
+  } else {
+    *h = h00 + (h11 - h01) * fu + (h01 - h00) * fv;
+    gx = (h11 - h01) / f.dx;
+    gy = (h01 - h00) / f.dx;
+  }
+  const float il = prsq(gx * gx + gy * gy + 1.0f);
+  *n = v3(-gx * il, -gy * il, il);
+}
+template <int T, int MN, int MC, int MG, int MP, int OBJ = 0, bool TGS = false, int LAY = 0, bool XF = false, bool HF = false>
+struct Team : TeamXf<XF>, TeamHf<HF> {
   using L = TeamLDSOf<T, MN, MC, OBJ, MG, MP, LAY>;
   using MT = ModelTile<MN, MG, MP, tile_hull_verts(OBJ)>;
   static constexpr int MR = L::MR;
@@ -1005,6 +1049,29 @@ struct Team : TeamXf<XF> {
     for (int b = 0; b < nb; b++)
       if (__shfl(bn, tb + b) == node && node >= 0) xfm |= 1ull << b;
     wsync();
+  }
+
+  // heightfield terrain (HF, TeamHf): the field and the env origin of this team's actor (`org3`: its row of
+  // env_origins, or nullptr for zero).  Once per launch
+  __device__ __forceinline__ void bind_hf(const HfDesc& f, const float* org3) {
+    static_assert(HF && OBJ == 0, "bind_hf: the heightfield instances have no free object");
+    this->hf = f;
+    this->hox = org3 ? org3[0] : 0.0f;
+    this->hoy = org3 ? org3[1] : 0.0f;
+    this->hoz = org3 ? org3[2] : 0.0f;
+    this->hcull = f.hmax - this->hoz;
+  }
+  // the ground under the actor-local point e (HF): the facet's normal, and the gap of a sphere of radius r at e
+  // against the facet's plane
+  __device__ __forceinline__ float hf_gap(V3 e, float r, V3* n) const {
+    float h;
+    hf_facet(this->hf, e.x + this->hox, e.y + this->hoy, &h, n);
+    return (e.z - (h - this->hoz)) * n->z - r;
+  }
+  // a geom's centre height over the highest ground there can be (the culls of collide()): over z = 0 for the plane
+  __device__ __forceinline__ float over_top(float cz) const {
+    if constexpr (HF) return cz - this->hcull;
+    else return cz;
   }
 
   __device__ __forceinline__ int col_of(int i) const { return ncol0 - 1 + i; }
@@ -2119,22 +2186,25 @@ struct Team : TeamXf<XF> {
         const int g = g0 + tl;
         V3 e0 = v3(0, 0, 0), e1 = v3(0, 0, 0);
         float r = 0.0f, d0 = 1e30f, d1 = 1e30f;
+        [[maybe_unused]] V3 n0 = v3(0, 0, 1), n1 = v3(0, 0, 1);  // (HF) the facets' normals
         if (g < G && (mt->gfil[g] & MG_COLLIDE_GROUND)) {
           V3 c;
           M3 Rg;
           geom_staged(g, &c, &Rg);
-          if (c.z - mt->gf[g][15] < off) {
+          if (over_top(c.z) - mt->gf[g][15] < off) {
             const float* gs = mt->gf[g] + 12;
             r = gs[0];
             if (mt->gtype[g] == MG_GT_CAPSULE) {
               const V3 ax = v3(Rg.m[0][2], Rg.m[1][2], Rg.m[2][2]) * gs[1];
               e0 = c - ax;
               e1 = c + ax;
-              d1 = e1.z - r;
+              if constexpr (HF) d1 = hf_gap(e1, r, &n1);
+              else d1 = e1.z - r;
             } else {
               e0 = c;
             }
-            d0 = e0.z - r;
+            if constexpr (HF) d0 = hf_gap(e0, r, &n0);
+            else d0 = e0.z - r;
           }
         }
         const bool k0 = d0 < off, k1 = d1 < off;
@@ -2143,9 +2213,14 @@ struct Team : TeamXf<XF> {
         const int incl = team_scan_bits<T, 2>(cnt, scan_tot);
         const int slot0 = base + incl - cnt;
         base += scan_tot;
-        if (k0 && slot0 < cap) put_contact(slot0, v3(e0.x, e0.y, e0.z - r), v3(0, 0, 1), d0, mt->gnode[g], g, -1, -1);
         const int s1 = slot0 + (k0 ? 1 : 0);
-        if (k1 && s1 < cap) put_contact(s1, v3(e1.x, e1.y, e1.z - r), v3(0, 0, 1), d1, mt->gnode[g], g, -1, -1);
+        if constexpr (HF) {
+          if (k0 && slot0 < cap) put_contact(slot0, e0 - n0 * r, n0, d0, mt->gnode[g], g, -1, -1);
+          if (k1 && s1 < cap) put_contact(s1, e1 - n1 * r, n1, d1, mt->gnode[g], g, -1, -1);
+        } else {
+          if (k0 && slot0 < cap) put_contact(slot0, v3(e0.x, e0.y, e0.z - r), v3(0, 0, 1), d0, mt->gnode[g], g, -1, -1);
+          if (k1 && s1 < cap) put_contact(s1, v3(e1.x, e1.y, e1.z - r), v3(0, 0, 1), d1, mt->gnode[g], g, -1, -1);
+        }
       }
     } else
     for (int g0 = 0; g0 < G; g0 += T) {
@@ -2158,12 +2233,12 @@ struct Team : TeamXf<XF> {
         // every candidate's gap is >= c.z - bounding radius: geoms that high cannot touch the plane; a box's lowest
         // corner exactly (Cartpole's 8 m rail: its bounding radius reaches the plane from any height), the same test
         // its corner loop would fail, so the same contacts
-        if (c.z - mt->gf[g][15] < off) ty = mt->gtype[g];
+        if (over_top(c.z) - mt->gf[g][15] < off) ty = mt->gtype[g];
         if (OBJ == 0 && ty == MG_GT_BOX) {  // (the hand instances' box geoms pass the radius test rarely: left as is)
           const float* hb = mt->gf[g] + 12;
           const float zlow = c.z - (fabsf(Rg.m[2][0]) * hb[0] + fabsf(Rg.m[2][1]) * hb[1] + fabsf(Rg.m[2][2]) * hb[2]);
           // (a rounding guard on the scale of the terms: the corner loop rounds its own sums)
-          if (!(zlow < off + 1e-6f * (1.0f + fabsf(c.z) + hb[0] + hb[1] + hb[2]))) ty = -1;
+          if (!(over_top(zlow) < off + 1e-6f * (1.0f + fabsf(c.z) + hb[0] + hb[1] + hb[2]))) ty = -1;
         }
       }
       const float* gs = g < G ? mt->gf[g] + 12 : mt->gf[0] + 12;
@@ -2195,13 +2270,20 @@ struct Team : TeamXf<XF> {
             e = c + mul(Rg, l);
             r = 0.0f;
           }
-          const float d = e.z - r;
+          [[maybe_unused]] V3 nf;  // (HF) the facet's normal
+          float d;
+          if constexpr (HF) d = hf_gap(e, r, &nf);
+          else d = e.z - r;
           if (!(d < off)) continue;
           if (pass == 0) {
             cnt++;
           } else {
             const int slot = slot0 + k;
-            if (slot < cap) put_contact(slot, v3(e.x, e.y, e.z - r), v3(0, 0, 1), d, mt->gnode[g], g, -1, -1);
+            if constexpr (HF) {
+              if (slot < cap) put_contact(slot, e - nf * r, nf, d, mt->gnode[g], g, -1, -1);
+            } else {
+              if (slot < cap) put_contact(slot, v3(e.x, e.y, e.z - r), v3(0, 0, 1), d, mt->gnode[g], g, -1, -1);
+            }
             k++;
           }
         }
@@ -3251,6 +3333,7 @@ struct Team : TeamXf<XF> {
   // is emitted.  Contacts between geoms are not predicted: the last substep's count stands in for them (none on Ant).
   // -1: not a ground_round model
   __device__ __forceinline__ int key_contacts() const {
+    static_assert(!HF, "key_contacts: the plane's tests; the heightfield kernels have no work ordering and do not call it");
     if (!mt->ground_round) return -1;
     const float off = p->contact_offset;
     const int G = mt->ng, cap = p->max_contacts < MC ? p->max_contacts : MC;

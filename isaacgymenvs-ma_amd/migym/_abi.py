@@ -179,6 +179,12 @@ class AnymalViews(C.Structure):
     _fields_ = [("commands", C.c_void_p), ("dof_targets", C.c_void_p)]
 
 
+class Heightfield(C.Structure):
+    """mg_heightfield: the terrain table of mg_sim_set_heightfield (device pointers, kept by the sim, not copied)."""
+    _fields_ = [("heights", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("dx", C.c_float), ("x0", C.c_float),
+                ("y0", C.c_float), ("hmax", C.c_float), ("env_origins", C.c_void_p)]
+
+
 MG_QUAD_DOFS, MG_QUAD_BODIES, MG_QUAD_OBS, MG_QUAD_ACTIONS, MG_QUAD_NOISE_COLS = 8, 9, 21, 12, 11
 
 
@@ -258,6 +264,9 @@ EXPORTS = {
     "mg_sim_bind": (C.c_int, [C.c_void_p, C.POINTER(StateViews)]),
     "mg_sim_simulate": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mg_sim_set_link_forces": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mg_heightfield_sizeof": (C.c_size_t, []),
+    "mg_sim_set_heightfield": (C.c_int, [C.c_void_p, C.POINTER(Heightfield)]),
+    "mg_height_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mg_sim_destroy": (C.c_int, [C.c_void_p]),
     "mg_set_indexed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mg_compute_observations": (C.c_int, [C.POINTER(TaskParams), C.c_int32] + [C.c_void_p] * 10 + [C.c_void_p]),
@@ -355,7 +364,8 @@ def check_layout(lib):
              "mg_anymal_views_sizeof": C.sizeof(AnymalViews), "mg_render_args_sizeof": C.sizeof(RenderArgs),
              "mg_amp_params_sizeof": C.sizeof(AmpParams), "mg_amp_views_sizeof": C.sizeof(AmpViews),
              "mg_quadcopter_params_sizeof": C.sizeof(QuadcopterParams),
-             "mg_quadcopter_views_sizeof": C.sizeof(QuadcopterViews)}
+             "mg_quadcopter_views_sizeof": C.sizeof(QuadcopterViews),
+             "mg_heightfield_sizeof": C.sizeof(Heightfield)}
     for fn, py in sizes.items():
         c = getattr(lib, fn)()
         if c != py:

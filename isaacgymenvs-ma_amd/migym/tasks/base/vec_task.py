@@ -24,7 +24,7 @@ from __future__ import annotations
 
 import abc
 import math
-from typing import Any, Dict, Tuple
+from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -354,6 +354,63 @@ class VecTask(DomainRandomizationMixin, Env):
         self._views.rb_forces, self._views.rb_force_space = forces.data_ptr(), int(space)
         _abi.check(self._lib.mg_sim_bind(self.sim, _abi.C.byref(self._views)), self._lib)
         _abi.check(self._lib.mg_sim_set_link_forces(self.sim, 1), self._lib)
+
+    def set_heightfield(self, heights: torch.Tensor, horizontal_scale: float, vertical_scale: float = 1.0,
+                        origin=(0.0, 0.0), env_origins: Optional[torch.Tensor] = None):
+        """Heightfield terrain under every later ``simulate`` (mg_sim_set_heightfield): ``heights`` is a
+        2-D device tensor (float, or int16 as ``isaacgym.terrain_utils`` makes it), ``heights[i, j] * vertical_scale``
+        metres at world ``(origin[0] + i * horizontal_scale, origin[1] + j * horizontal_scale)`` -- the index order of
+        the reference's ``height_samples``.  ``env_origins`` (num_actors, 3): where each actor's frame sits in the
+        world; zero without it.  The table is converted once to contiguous fp32 and kept; a later change of
+        ``heights`` needs another call.  Only the tasks that step through mg_sim_simulate take a field: the fused
+        tasks (Ant, Humanoid, MAAnt, Cartpole, ShadowHand) raise.  Rendering still draws the plane z = 0."""
+        if not self.steps_through_simulate:
+            raise NotImplementedError(f"{self.task_name}: a heightfield is not built for the fused step kernel "
+                                      "(mg_env_step) this task runs; mg_sim_simulate takes it, which the three-launch "
+                                      "tasks (Anymal, HumanoidAMP, Quadcopter, FrankaReachMA) step through")
+        dev = torch.device(self.device)
+        if not (isinstance(heights, torch.Tensor) and heights.dim() == 2 and min(heights.shape) >= 2):
+            raise ValueError("set_heightfield: heights must be a 2-D tensor of at least 2 x 2 samples")
+        if heights.device != dev:
+            raise ValueError(f"set_heightfield: heights must be on {self.device}")
+        if not (heights.dtype == torch.int16 or heights.is_floating_point()):
+            raise ValueError("set_heightfield: heights must be a float or int16 tensor")
+        if not (horizontal_scale > 0.0 and horizontal_scale < float("inf")):
+            raise ValueError("set_heightfield: horizontal_scale must be positive and finite")
+        if env_origins is not None:
+            if not (isinstance(env_origins, torch.Tensor) and env_origins.device == dev
+                    and tuple(env_origins.shape) == (self.num_actors, 3)):
+                raise ValueError(f"set_heightfield: env_origins must be a ({self.num_actors}, 3) tensor on {self.device}")
+            env_origins = env_origins.to(torch.float32).contiguous()
+        table = (heights.float() * vertical_scale).contiguous()
+        hf = _abi.Heightfield(heights=table.data_ptr(), nx=table.shape[0], ny=table.shape[1], dx=float(horizontal_scale),
+                              x0=float(origin[0]), y0=float(origin[1]), hmax=float(table.max()),
+                              env_origins=_abi.ptr(env_origins))
+        _abi.check(self._lib.mg_sim_set_heightfield(self.sim, _abi.C.byref(hf)), self._lib)
+        self._heightfield = (table, env_origins)   # alive while the sim reads them
+
+    def clear_heightfield(self):
+        """back to the ground plane z = 0"""
+        _abi.check(self._lib.mg_sim_set_heightfield(self.sim, None), self._lib)
+        self._heightfield = None
+
+    def height_scan(self, points: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(num_actors, P) terrain heights under ``points`` (P, 2), a pattern in each actor's yaw frame around its root
+        (the reference's get_heights, anymal_terrain.py:515-538; mg_height_scan), in the actor's frame.  Asynchronous
+        on the caller's stream."""
+        dev = torch.device(self.device)
+        if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[1] == 2 and points.device == dev):
+            raise ValueError(f"height_scan: points must be a (P, 2) tensor on {self.device}")
+        points = points.to(torch.float32).contiguous()
+        P = points.shape[0]
+        if out is None:
+            out = torch.empty((self.num_actors, P), device=dev, dtype=torch.float32)
+        elif not (out.dtype == torch.float32 and out.is_contiguous() and out.device == dev
+                  and tuple(out.shape) == (self.num_actors, P)):
+            raise ValueError(f"height_scan: out must be a contiguous fp32 ({self.num_actors}, {P}) tensor on {self.device}")
+        _abi.check(self._lib.mg_height_scan(self.sim, points.data_ptr(), P, out.data_ptr(),
+                                            torch.cuda.current_stream().cuda_stream), self._lib)
+        return out
 
     def _dynamics(self):
         """the task's DynamicsTensors (migym/dynamics.py); free-base tasks raise NotImplementedError with the
