@@ -94,44 +94,33 @@ def build(force=False, verbose=False, timing=False, variant=None, defines=(), ex
     objdir = os.path.join(HERE, "build", ("var_" + variant) if variant else ("timing" if timing else "release"))
     os.makedirs(objdir, exist_ok=True)
     objs, cmds = [], []
-    ninst = num_instances()
-    # -1: migym.hip; 0 .. ninst - 1: the instances; ninst .. 2 ninst - 1: each instance's contact read-out (k_contacts,
-    # -DMG_CONTACTS_TU: a test aid in code objects of its own, linked last, so the code objects before them are
-    # byte for byte what they are without it)
-    for j in range(-1, 2 * ninst):
-        i = j if j < ninst else j - ninst
-        o = os.path.join(objdir, "migym.o" if j < 0 else (f"inst{i}.o" if j < ninst else f"contacts{i}.o"))
-        src = SRC if j < 0 else INST
-        # instance TUs: no MachineLICM.  The work-queue kernels' per-item body sits in a loop, and the pass hoists
-        # values out of it into registers held across all items (Humanoid: 48 spilled VGPRs vs 25 without it;
-        # measured +3 % ShadowHand, +2 % egg, +1 % Humanoid, Ant unchanged)
-        # and no interprocedural register allocation (a guard only: a real call in these kernels miscompiled in
-        # round 3 with IPRA on -- wrong object states -- and, with the cause not pinned down, with IPRA off too:
-        # an illegal address and a 93 % parity build).  Every phase is force-inlined, and
-        # codeobj.check_no_calls below fails the build if any call is left in the device code
-        inst = [] if j < 0 else [f"-DMG_INST={i}", "-mllvm", "-disable-machine-licm", "-mllvm", "-enable-ipra=false"]
-        if j >= ninst:
-            inst.append("-DMG_CONTACTS_TU")
-        cmds.append([hipcc] + flags + inst + ["-c", "-o", o, src])
-        objs.append(o)
-    # ... and after them the link-force variants of k_simulate (-DMG_LINKFORCE_TU, mg_sim_set_link_forces): the
-    # objectless instances in the classic layout, again in code objects of their own
-    for i in linkforce_instances():
-        o = os.path.join(objdir, f"linkforce{i}.o")
-        cmds.append([hipcc] + flags + [f"-DMG_INST={i}", "-mllvm", "-disable-machine-licm", "-mllvm", "-enable-ipra=false",
-                                       "-DMG_LINKFORCE_TU", "-c", "-o", o, INST])
-        objs.append(o)
-    # ... and last the heightfield variants (-DMG_HEIGHTFIELD_TU, mg_sim_set_heightfield): k_simulate_hf and the contact
-    # read-out that goes with it, for the same instances
-    for i in linkforce_instances():
-        o = os.path.join(objdir, f"heightfield{i}.o")
-        cmds.append([hipcc] + flags + [f"-DMG_INST={i}", "-mllvm", "-disable-machine-licm", "-mllvm", "-enable-ipra=false",
-                                       "-DMG_HEIGHTFIELD_TU", "-c", "-o", o, INST])
-        objs.append(o)
-    # ... and mg_height_scan's kernel (height_scan.hip)
-    o = os.path.join(objdir, "height_scan.o")
-    cmds.append([hipcc] + flags + ["-c", "-o", o, SCAN])
-    objs.append(o)
+
+    def unit(name, src, *args):
+        objs.append(os.path.join(objdir, name + ".o"))
+        cmds.append([hipcc] + flags + list(args) + ["-c", "-o", objs[-1], src])
+
+    # instance TUs: no MachineLICM.  The work-queue kernels' per-item body sits in a loop, and the pass hoists
+    # values out of it into registers held across all items (Humanoid: 48 spilled VGPRs vs 25 without it;
+    # measured +3 % ShadowHand, +2 % egg, +1 % Humanoid, Ant unchanged)
+    # and no interprocedural register allocation (a guard only: a real call in these kernels miscompiled in
+    # round 3 with IPRA on -- wrong object states -- and, with the cause not pinned down, with IPRA off too:
+    # an illegal address and a 93 % parity build).  Every phase is force-inlined, and
+    # codeobj.check_no_calls below fails the build if any call is left in the device code
+    inst_flags = ["-mllvm", "-disable-machine-licm", "-mllvm", "-enable-ipra=false"]
+    every, classic = range(num_instances()), linkforce_instances()
+    # the kinds of instance TU, in link order (object-file prefix, define, instances).  Every kind after the first
+    # sits in code objects of its own, linked after it, so the shipped instances' code objects are byte for byte
+    # what they are without them; the order of objs fixes the code objects' order in the fat binary, by which
+    # codeobj.diff pairs them
+    kinds = (("inst", None, every),                                # k_simulate, k_env_step / k_hand_step
+             ("contacts", "MG_CONTACTS_TU", every),                # k_contacts (mg_debug_contacts: a test aid)
+             ("linkforce", "MG_LINKFORCE_TU", classic),            # k_simulate_xf (mg_sim_set_link_forces)
+             ("heightfield", "MG_HEIGHTFIELD_TU", classic))        # k_simulate_hf, k_contacts_hf (mg_sim_set_heightfield)
+    unit("migym", SRC)
+    for prefix, define, instances in kinds:
+        for i in instances:
+            unit(f"{prefix}{i}", INST, f"-DMG_INST={i}", *inst_flags, *(["-D" + define] if define else []))
+    unit("height_scan", SCAN)  # mg_height_scan's kernel
     _run_parallel(cmds, verbose)
     subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out + ".tmp"] + objs)
     sys.path.insert(0, HERE)

@@ -1,6 +1,9 @@
 // dispatch.hpp — the kernel instances (one per model capacity) and the host entry points each
 // instance translation unit exports.  migym.hip sees only these declarations; inst.hip compiles
 // one instance per translation unit (build.py runs them in parallel) from step_kernels.hpp.
+// The launchers (Run*) are defined there over shared helpers; the three functors below that refuse every instance but
+// the objectless classic ones (SimulateXF, SimulateHF, ContactsHF) stay three plain structs: they differ in the
+// launcher, its arguments and the error text, and one template over those three reads no shorter.
 #pragma once
 #include "common.hpp"
 

@@ -4,7 +4,8 @@
 // only) -- a code object of its own, so that the shipped instances' code objects are what they are without it.
 // With -DMG_LINKFORCE_TU it holds the instance's k_simulate with link forces alone (k_simulate_xf), likewise.
 // With -DMG_HEIGHTFIELD_TU it holds the instance's k_simulate on heightfield terrain and that kernel's contact read-out
-// alone (k_simulate_hf, k_contacts_hf), likewise.
+// alone (k_simulate_hf, k_contacts_hf), likewise.  The four kinds of unit are one table in build.py (`kinds`), and the
+// five kernels are wrappers over one body (step_kernels.hpp).
 #include "step_kernels.hpp"
 
 #ifndef MG_INST

@@ -1,11 +1,13 @@
 // step_kernels.hpp — the team kernels of the hot path (one team of T lanes per actor):
-//   k_simulate   gym.simulate alone
+//   k_simulate   gym.simulate alone; k_simulate_xf with link forces, k_simulate_hf on heightfield terrain, and the
+//                contact read-outs k_contacts / k_contacts_hf: five entry points over one shared body
 //   k_env_step   the whole VecTask.step of the locomotion tasks (Ant, Humanoid, Cartpole, MA-Ant)
 //   k_hand_step  the whole VecTask.step of ShadowHand
-// plus the host launchers RunSimulate / RunEnvStep (dispatch.hpp).  Included only by inst.hip, which
+// plus the host launchers Run* (dispatch.hpp).  Included only by inst.hip, which
 // instantiates one capacity instance per translation unit.
 #pragma once
 #include <new>
+#include <type_traits>
 
 #include "dispatch.hpp"
 #include "hand_task.hpp"
@@ -153,63 +155,151 @@ __device__ __forceinline__ void wq_done(unsigned* wq, int grid_waves) {
 }
 
 // ------------------------------------------------------------------------------------------------ kernels
-// gym.simulate: one team of T lanes per actor (team_physics.hpp).  OBJ: hand-task envs with root
-// rows [articulation, object, goal], PD targets and rigid-body rows [bodies..., object, goal].
-template <int T, int MN, int MC, int MG, int MP, int OBJ, bool DR, bool TGS = false, int LAY = 0>
-__global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, OBJ, DR, LAY>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, OBJ, DR, LAY>::kWPE))) void k_simulate(
-    const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n) {
-  using SH = Shape<T, MN, MC, MG, MP, OBJ, DR, LAY>;
-  constexpr int E = SH::E, W = SH::W;
-  constexpr int ROWS = OBJ ? 3 : 1;
-  __shared__ mg::BankSlot<mg::TeamLDSOf<T, MN, MC, OBJ, MG, MP, LAY>, T> lds[E];
-  __shared__ typename mg::Team<T, MN, MC, MG, MP, OBJ>::MT tile;
-  __shared__ mg::DrTile<DR ? MN : 1, DR ? MG : 1> drt[DR ? E : 1];
-  mg::copy_tile(&tile, static_cast<const typename mg::Team<T, MN, MC, MG, MP, OBJ>::MT*>(timg));
-  __syncthreads();  // the only block-wide barrier: every later phase synchronises its own wave
-  const int team = threadIdx.x / T;
-  const int a = blockIdx.x * E + team;
-  const bool valid = a < n;
-  const int ac = valid ? a : n - 1;
-  const int nd = m->num_dofs, ns = m->num_sensors;
-  mg::Team<T, MN, MC, MG, MP, OBJ, TGS, LAY> t;
-  t.init(&lds[team].v, &tile, m, &p);
-  if constexpr (DR) {  // domain randomization: this actor's env_props row into the team's DrTile
-    mg::load_dr<T>(&drt[team], v.env_props + (size_t)v.env_props_stride * ac, m, t.tl);
-    t.bind_dr(&drt[team]);
-  }
-  if (OBJ && t.tl < 4) {  // applied force on the object row of rb_forces (apply_rigid_body_force_tensors)
-    const float* fr = v.rb_forces ? v.rb_forces + ((size_t)(m->num_bodies + 2) * ac + m->num_bodies) * 3 : nullptr;
-    lds[team].v.oforce[t.tl] = t.tl < 3 ? (fr ? fr[t.tl] : 0.0f) : (v.rb_force_space == MG_LOCAL_SPACE ? 1.0f : 0.0f);
+// The gym.simulate kernels (k_simulate, k_simulate_xf, k_simulate_hf) and the contact read-outs (k_contacts,
+// k_contacts_hf) are one program: each kernel below declares its LDS, names its Team type, binds what its feature
+// adds (env_props rows, link-force rows, the heightfield) and runs the shared pieces that follow.  The pieces know
+// nothing of the kernel that calls them: the Team's own compile-time flags carry every difference.  A new variant
+// is a new wrapper.  Scalars travel by value (TeamSlot) and __restrict__ stays on the kernels' own parameters: with
+// the model's counts reloaded after the stores the kernels' register use moved (DESIGN.md §3b k_simulate).
+
+// a team's place in the launch, and the model's counts (read once, ahead of everything that stores)
+struct TeamSlot {
+  int team;        // the team's index in its block
+  int a, ac;       // its actor, and the actor it loads: n - 1 for a team past the batch, which writes nothing
+  bool valid;      // a < n
+  int nd, ns, nb;  // the model's DOFs, sensors and bodies
+};
+
+// the prologue: the block's model tile, the only block-wide barrier (every later phase synchronises its own wave),
+// and the team's slot (T lanes per team, E teams per block).  Team::init() on the slot's LDS follows in the kernel
+// itself, as the substep loop does later: inlined through a helper, either is compiled to other code -- init() to
+// another pairing of the products the compiler fuses into FMAs in the substeps, which moves result bits; substep()
+// to another register allocation (DESIGN.md §3b k_simulate)
+template <int T, int E, class MT>
+__device__ __forceinline__ TeamSlot team_enter(MT* tile, const void* timg, const mg_model* m, int n) {
+  mg::copy_tile(tile, static_cast<const MT*>(timg));
+  __syncthreads();
+  TeamSlot k;
+  k.team = threadIdx.x / T;
+  k.a = blockIdx.x * E + k.team;
+  k.valid = k.a < n;
+  k.ac = k.valid ? k.a : n - 1;
+  k.nd = m->num_dofs, k.ns = m->num_sensors, k.nb = m->num_bodies;
+  return k;
+}
+
+// the free object's applied force, from its row of rb_forces (apply_rigid_body_force_tensors), into the team's LDS;
+// then the wave sync that publishes it, and the DrTile rows of a caller that loaded them, to the team
+template <class TM>
+__device__ __forceinline__ void stage_object_force(TM& t, const mg_state_views& v, const TeamSlot& k) {
+  if (TM::kObj && t.tl < 4) {
+    const float* fr = v.rb_forces ? v.rb_forces + ((size_t)(k.nb + 2) * k.ac + k.nb) * 3 : nullptr;
+    t.s->oforce[t.tl] = t.tl < 3 ? (fr ? fr[t.tl] : 0.0f) : (v.rb_force_space == MG_LOCAL_SPACE ? 1.0f : 0.0f);
   }
   mg::wsync();
-  float* root = v.root_states + (size_t)13 * ROWS * ac;
-  t.load(root, v.dof_state + (size_t)2 * nd * ac, v.dof_actuation ? v.dof_actuation + (size_t)nd * ac : nullptr,
-         OBJ ? root + 13 : nullptr, v.dof_targets ? v.dof_targets + (size_t)nd * ac : nullptr);
-  for (int st = 0; st < p.substeps; st++) t.substep();
-  t.outputs(lds[team].v.st().sens, lds[team].v.st().dforce,
-            (valid && v.net_contact_forces) ? v.net_contact_forces + (size_t)3 * (m->num_bodies + (OBJ ? 2 : 0)) * a
-                                            : nullptr);
+}
+
+// Team::load() on the actor's rows of the state views; returns its root rows.  OBJ: hand-task envs with root rows
+// [articulation, object, goal]
+template <class TM>
+__device__ __forceinline__ float* load_actor(TM& t, const mg_state_views& v, const TeamSlot& k) {
+  constexpr int ROWS = TM::kObj ? 3 : 1;
+  float* root = v.root_states + (size_t)13 * ROWS * k.ac;
+  t.load(root, v.dof_state + (size_t)2 * k.nd * k.ac, v.dof_actuation ? v.dof_actuation + (size_t)k.nd * k.ac : nullptr,
+         TM::kObj ? root + 13 : nullptr, v.dof_targets ? v.dof_targets + (size_t)k.nd * k.ac : nullptr);
+  return root;
+}
+
+// the end of gym.simulate, after the team's substeps: the outputs, and the team-cooperative write-back to the state
+// views (gym layouts).  OBJ: rigid-body rows [bodies..., object, goal].  The substep loop itself stays in each kernel:
+// Team::substep() inlined through a helper, not straight into the kernel, is allocated differently (every k_simulate
+// one VGPR more, the 8-lane and the compact 32-lane TGS instances more spills)
+template <class TM>
+__device__ __forceinline__ void finish_actor(TM& t, const mg_model* m, const mg_state_views& v, const TeamSlot& k,
+                                             float* root) {
+  constexpr int T = TM::kT, OBJ = TM::kObj;
+  const int a = k.a, nd = k.nd, ns = k.ns, nb = k.nb, nbe = nb + (OBJ ? 2 : 0);
+  auto& L = *t.s;
+  t.outputs(L.st().sens, L.st().dforce,
+            (k.valid && v.net_contact_forces) ? v.net_contact_forces + (size_t)3 * nbe * a : nullptr);
   t.stage_state();
   mg::wsync();
-  if (valid) {
-    auto& L = lds[team].v;
+  if (k.valid) {
     if (!m->fixed_base)
-      for (int k = t.tl; k < 13; k += T) root[k] = L.st().root[k];
+      for (int q = t.tl; q < 13; q += T) root[q] = L.st().root[q];
     if (OBJ)
-      for (int k = t.tl; k < 13; k += T) root[13 + k] = L.oroot[k];
-    for (int k = t.tl; k < 2 * nd; k += T) v.dof_state[(size_t)2 * nd * a + k] = L.st().dof[k];
+      for (int q = t.tl; q < 13; q += T) root[13 + q] = L.oroot[q];
+    for (int q = t.tl; q < 2 * nd; q += T) v.dof_state[(size_t)2 * nd * a + q] = L.st().dof[q];
     if (v.sensors)
-      for (int k = t.tl; k < 6 * ns; k += T) v.sensors[(size_t)6 * ns * a + k] = L.st().sens[k];
+      for (int q = t.tl; q < 6 * ns; q += T) v.sensors[(size_t)6 * ns * a + q] = L.st().sens[q];
     if (v.dof_force)
-      for (int k = t.tl; k < nd; k += T) v.dof_force[(size_t)nd * a + k] = L.st().dforce[k];
+      for (int q = t.tl; q < nd; q += T) v.dof_force[(size_t)nd * a + q] = L.st().dforce[q];
     if (v.rigid_body_states) {
-      const int nb = m->num_bodies, nbe = nb + (OBJ ? 2 : 0);
       float* rb = v.rigid_body_states + (size_t)13 * nbe * a;
       for (int b = t.tl; b < nb; b += T) t.body_state(b, rb + 13 * b);
       if (OBJ)
-        for (int k = t.tl; k < 26; k += T) rb[13 * nb + k] = k < 13 ? L.oroot[k] : root[26 + k - 13];
+        for (int q = t.tl; q < 26; q += T) rb[13 * nb + q] = q < 13 ? L.oroot[q] : root[26 + q - 13];
     }
   }
+}
+
+// the contact list of a loaded team's first substep, per actor: the front half of Team::substep() up to collide() --
+// THE CALL SEQUENCE BELOW REPEATS Team::substep()'s (team_physics.hpp): change both together.  Rows (nodeA, geomA,
+// nodeB, geomB, p[3], n[3], gap) as the oracle's orc_contacts_full; the ids sign-extended from cside (-1 ground, -2
+// the object).  Nothing is written back to the state views.
+template <class TM>
+__device__ __forceinline__ void contacts_actor(TM& t, const TeamSlot& k, float* out, int* count, int cap) {
+  t.hull_stage();
+  t.fk();
+  if constexpr (TM::kObj == MG_GT_ELLIPSOID) {
+    t.egg_stage();
+    t.reload_tree();
+  }
+  t.set_axis();
+  if (TM::kObj) t.tendons();
+  t.aba();
+  t.obj_free();
+  t.collide();  // ends with a wave sync: s->ncon and the list are visible to the team
+  if (k.valid) {
+    auto& L = *t.s;
+    const int nc = L.ncon;
+    if (t.tl == 0) count[k.a] = nc;
+    for (int c = t.tl; c < nc && c < cap; c += TM::kT) {
+      float* o = out + ((size_t)k.a * cap + c) * 11;
+      o[0] = (float)t.cside(c, 0);
+      o[1] = (float)t.cside(c, 2);
+      o[2] = (float)t.cside(c, 1);
+      o[3] = (float)t.cside(c, 3);
+      for (int j = 0; j < 3; j++) {
+        o[4 + j] = L.cp[c][j];
+        o[7 + j] = L.cn[c][j];
+      }
+      o[10] = L.gap(c);
+    }
+  }
+}
+
+// gym.simulate: one team of T lanes per actor (team_physics.hpp).  DR: domain randomization, this actor's env_props
+// row in the team's DrTile
+template <int T, int MN, int MC, int MG, int MP, int OBJ, bool DR, bool TGS = false, int LAY = 0>
+__global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, OBJ, DR, LAY>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, OBJ, DR, LAY>::kWPE))) void k_simulate(
+    const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n) {
+  constexpr int E = Shape<T, MN, MC, MG, MP, OBJ, DR, LAY>::E;
+  using TM = mg::Team<T, MN, MC, MG, MP, OBJ, TGS, LAY>;
+  __shared__ mg::BankSlot<typename TM::L, T> lds[E];
+  __shared__ typename TM::MT tile;
+  __shared__ mg::DrTile<DR ? MN : 1, DR ? MG : 1> drt[DR ? E : 1];
+  const TeamSlot k = team_enter<T, E>(&tile, timg, m, n);
+  TM t;
+  t.init(&lds[k.team].v, &tile, m, &p);
+  if constexpr (DR) {
+    mg::load_dr<T>(&drt[k.team], v.env_props + (size_t)v.env_props_stride * k.ac, m, t.tl);
+    t.bind_dr(&drt[k.team]);
+  }
+  stage_object_force(t, v, k);
+  float* root = load_actor(t, v, k);
+  for (int st = 0; st < p.substeps; st++) t.substep();
+  finish_actor(t, m, v, k, root);
 }
 
 // gym.simulate with link forces (mg_sim_set_link_forces): k_simulate's objectless, non-DR instance in the classic
@@ -219,50 +309,25 @@ __global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, OBJ, DR, LAY>::kThreads))
 template <int T, int MN, int MC, int MG, int MP, bool TGS = false>
 __global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>::kWPE))) void k_simulate_xf(
     const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n) {
-  using SH = Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>;
-  constexpr int E = SH::E;
-  __shared__ mg::BankSlot<mg::TeamLDSOf<T, MN, MC, 0, MG, MP, 0>, T> lds[E];
-  __shared__ typename mg::Team<T, MN, MC, MG, MP, 0>::MT tile;
+  constexpr int E = Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>::E;
+  using TM = mg::Team<T, MN, MC, MG, MP, 0, TGS, 0, true>;
+  __shared__ mg::BankSlot<typename TM::L, T> lds[E];
+  __shared__ typename TM::MT tile;
   __shared__ float xf[E][6 * MN];
-  mg::copy_tile(&tile, static_cast<const typename mg::Team<T, MN, MC, MG, MP, 0>::MT*>(timg));
-  __syncthreads();
-  const int team = threadIdx.x / T;
-  const int a = blockIdx.x * E + team;
-  const bool valid = a < n;
-  const int ac = valid ? a : n - 1;
-  const int nd = m->num_dofs, ns = m->num_sensors, nb = m->num_bodies;  // nb <= MN (RunSimulateXF)
-  mg::Team<T, MN, MC, MG, MP, 0, TGS, 0, true> t;
-  t.init(&lds[team].v, &tile, m, &p);
+  const TeamSlot k = team_enter<T, E>(&tile, timg, m, n);
+  TM t;
+  t.init(&lds[k.team].v, &tile, m, &p);
   {
-    const float* fr = v.rb_forces + (size_t)3 * nb * ac;
-    for (int k = t.tl; k < 3 * nb; k += T) xf[team][k] = fr[k];
+    const float* fr = v.rb_forces + (size_t)3 * k.nb * k.ac;  // nb <= MN (RunSimulateXF)
+    for (int q = t.tl; q < 3 * k.nb; q += T) xf[k.team][q] = fr[q];
     mg::wsync();
-    const mg::V3 f = t.tl < nb ? mg::ld3(&xf[team][3 * t.tl]) : mg::v3(0.0f, 0.0f, 0.0f);
+    const mg::V3 f = t.tl < k.nb ? mg::ld3(&xf[k.team][3 * t.tl]) : mg::v3(0.0f, 0.0f, 0.0f);
     mg::wsync();  // every lane holds its row: bind_xf() overwrites them
-    t.bind_xf(xf[team], f, v.rb_force_space == MG_LOCAL_SPACE);
+    t.bind_xf(xf[k.team], f, v.rb_force_space == MG_LOCAL_SPACE);
   }
-  float* root = v.root_states + (size_t)13 * ac;
-  t.load(root, v.dof_state + (size_t)2 * nd * ac, v.dof_actuation ? v.dof_actuation + (size_t)nd * ac : nullptr, nullptr,
-         v.dof_targets ? v.dof_targets + (size_t)nd * ac : nullptr);
+  float* root = load_actor(t, v, k);
   for (int st = 0; st < p.substeps; st++) t.substep();
-  t.outputs(lds[team].v.st().sens, lds[team].v.st().dforce,
-            (valid && v.net_contact_forces) ? v.net_contact_forces + (size_t)3 * nb * a : nullptr);
-  t.stage_state();
-  mg::wsync();
-  if (valid) {
-    auto& L = lds[team].v;
-    if (!m->fixed_base)
-      for (int k = t.tl; k < 13; k += T) root[k] = L.st().root[k];
-    for (int k = t.tl; k < 2 * nd; k += T) v.dof_state[(size_t)2 * nd * a + k] = L.st().dof[k];
-    if (v.sensors)
-      for (int k = t.tl; k < 6 * ns; k += T) v.sensors[(size_t)6 * ns * a + k] = L.st().sens[k];
-    if (v.dof_force)
-      for (int k = t.tl; k < nd; k += T) v.dof_force[(size_t)nd * a + k] = L.st().dforce[k];
-    if (v.rigid_body_states) {
-      float* rb = v.rigid_body_states + (size_t)13 * nb * a;
-      for (int b = t.tl; b < nb; b += T) t.body_state(b, rb + 13 * b);
-    }
-  }
+  finish_actor(t, m, v, k, root);
 }
 
 // gym.simulate on heightfield terrain (mg_sim_set_heightfield): k_simulate's objectless, non-DR instance in the classic
@@ -273,151 +338,52 @@ template <int T, int MN, int MC, int MG, int MP, bool TGS = false>
 __global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, 0, false, 0>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, 0, false, 0>::kWPE))) void k_simulate_hf(
     const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n, mg::HfDesc hf,
     const float* __restrict__ env_origins) {
-  using SH = Shape<T, MN, MC, MG, MP, 0, false, 0>;
-  constexpr int E = SH::E;
-  __shared__ mg::BankSlot<mg::TeamLDSOf<T, MN, MC, 0, MG, MP, 0>, T> lds[E];
-  __shared__ typename mg::Team<T, MN, MC, MG, MP, 0>::MT tile;
-  mg::copy_tile(&tile, static_cast<const typename mg::Team<T, MN, MC, MG, MP, 0>::MT*>(timg));
-  __syncthreads();
-  const int team = threadIdx.x / T;
-  const int a = blockIdx.x * E + team;
-  const bool valid = a < n;
-  const int ac = valid ? a : n - 1;
-  const int nd = m->num_dofs, ns = m->num_sensors, nb = m->num_bodies;
-  mg::Team<T, MN, MC, MG, MP, 0, TGS, 0, false, true> t;
-  t.init(&lds[team].v, &tile, m, &p);
-  t.bind_hf(hf, env_origins ? env_origins + (size_t)3 * ac : nullptr);
-  float* root = v.root_states + (size_t)13 * ac;
-  t.load(root, v.dof_state + (size_t)2 * nd * ac, v.dof_actuation ? v.dof_actuation + (size_t)nd * ac : nullptr, nullptr,
-         v.dof_targets ? v.dof_targets + (size_t)nd * ac : nullptr);
+  constexpr int E = Shape<T, MN, MC, MG, MP, 0, false, 0>::E;
+  using TM = mg::Team<T, MN, MC, MG, MP, 0, TGS, 0, false, true>;
+  __shared__ mg::BankSlot<typename TM::L, T> lds[E];
+  __shared__ typename TM::MT tile;
+  const TeamSlot k = team_enter<T, E>(&tile, timg, m, n);
+  TM t;
+  t.init(&lds[k.team].v, &tile, m, &p);
+  t.bind_hf(hf, env_origins ? env_origins + (size_t)3 * k.ac : nullptr);
+  float* root = load_actor(t, v, k);
   for (int st = 0; st < p.substeps; st++) t.substep();
-  t.outputs(lds[team].v.st().sens, lds[team].v.st().dforce,
-            (valid && v.net_contact_forces) ? v.net_contact_forces + (size_t)3 * nb * a : nullptr);
-  t.stage_state();
-  mg::wsync();
-  if (valid) {
-    auto& L = lds[team].v;
-    if (!m->fixed_base)
-      for (int k = t.tl; k < 13; k += T) root[k] = L.st().root[k];
-    for (int k = t.tl; k < 2 * nd; k += T) v.dof_state[(size_t)2 * nd * a + k] = L.st().dof[k];
-    if (v.sensors)
-      for (int k = t.tl; k < 6 * ns; k += T) v.sensors[(size_t)6 * ns * a + k] = L.st().sens[k];
-    if (v.dof_force)
-      for (int k = t.tl; k < nd; k += T) v.dof_force[(size_t)nd * a + k] = L.st().dforce[k];
-    if (v.rigid_body_states) {
-      float* rb = v.rigid_body_states + (size_t)13 * nb * a;
-      for (int b = t.tl; b < nb; b += T) t.body_state(b, rb + 13 * b);
-    }
-  }
+  finish_actor(t, m, v, k, root);
 }
 
-// mg_debug_contacts while a heightfield is set (tests only): k_contacts below for k_simulate_hf -- the same call
-// sequence (change them together), rows and launch shape
-template <int T, int MN, int MC, int MG, int MP>
-__global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, 0, false, 0>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, 0, false, 0>::kWPE))) void k_contacts_hf(
-    const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n, mg::HfDesc hf,
-    const float* __restrict__ env_origins, float* __restrict__ out, int* __restrict__ count, int cap) {
-  using SH = Shape<T, MN, MC, MG, MP, 0, false, 0>;
-  constexpr int E = SH::E;
-  __shared__ mg::BankSlot<mg::TeamLDSOf<T, MN, MC, 0, MG, MP, 0>, T> lds[E];
-  __shared__ typename mg::Team<T, MN, MC, MG, MP, 0>::MT tile;
-  mg::copy_tile(&tile, static_cast<const typename mg::Team<T, MN, MC, MG, MP, 0>::MT*>(timg));
-  __syncthreads();
-  const int team = threadIdx.x / T;
-  const int a = blockIdx.x * E + team;
-  const bool valid = a < n;
-  const int ac = valid ? a : n - 1;
-  const int nd = m->num_dofs;
-  mg::Team<T, MN, MC, MG, MP, 0, false, 0, false, true> t;
-  t.init(&lds[team].v, &tile, m, &p);
-  t.bind_hf(hf, env_origins ? env_origins + (size_t)3 * ac : nullptr);
-  float* root = v.root_states + (size_t)13 * ac;
-  t.load(root, v.dof_state + (size_t)2 * nd * ac, v.dof_actuation ? v.dof_actuation + (size_t)nd * ac : nullptr, nullptr,
-         v.dof_targets ? v.dof_targets + (size_t)nd * ac : nullptr);
-  t.hull_stage();
-  t.fk();
-  t.set_axis();
-  t.aba();
-  t.obj_free();
-  t.collide();  // ends with a wave sync: s->ncon and the list are visible to the team
-  if (valid) {
-    auto& L = lds[team].v;
-    const int nc = L.ncon;
-    if (t.tl == 0) count[a] = nc;
-    for (int c = t.tl; c < nc && c < cap; c += T) {
-      float* o = out + ((size_t)a * cap + c) * 11;
-      o[0] = (float)t.cside(c, 0);
-      o[1] = (float)t.cside(c, 2);
-      o[2] = (float)t.cside(c, 1);
-      o[3] = (float)t.cside(c, 3);
-      for (int k = 0; k < 3; k++) {
-        o[4 + k] = L.cp[c][k];
-        o[7 + k] = L.cn[c][k];
-      }
-      o[10] = L.gap(c);
-    }
-  }
-}
-
-// mg_debug_contacts (tests only): the contact list of the first substep of k_simulate, per actor.  The same Team,
-// LDS layout, model tile, init / load and launch shape as k_simulate above, and the front half of
-// Team::substep() up to collide() -- THE CALL SEQUENCE BELOW REPEATS Team::substep()'s (team_physics.hpp): change
-// both together.  Rows (nodeA, geomA, nodeB, geomB, p[3], n[3], gap) as the oracle's orc_contacts_full; the ids
-// sign-extended from cside (-1 ground, -2 the object).  Nothing is written back to the state views.
+// mg_debug_contacts (tests only): the contact list of the first substep of k_simulate, per actor: the same Team, LDS
+// layout, model tile, init / load and launch shape as k_simulate's non-DR PGS instance
 template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY = 0>
 __global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, OBJ, false, LAY>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, OBJ, false, LAY>::kWPE))) void k_contacts(
     const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n,
     float* __restrict__ out, int* __restrict__ count, int cap) {
-  using SH = Shape<T, MN, MC, MG, MP, OBJ, false, LAY>;
-  constexpr int E = SH::E;
-  constexpr int ROWS = OBJ ? 3 : 1;
-  __shared__ mg::BankSlot<mg::TeamLDSOf<T, MN, MC, OBJ, MG, MP, LAY>, T> lds[E];
-  __shared__ typename mg::Team<T, MN, MC, MG, MP, OBJ>::MT tile;
-  mg::copy_tile(&tile, static_cast<const typename mg::Team<T, MN, MC, MG, MP, OBJ>::MT*>(timg));
-  __syncthreads();
-  const int team = threadIdx.x / T;
-  const int a = blockIdx.x * E + team;
-  const bool valid = a < n;
-  const int ac = valid ? a : n - 1;
-  const int nd = m->num_dofs;
-  mg::Team<T, MN, MC, MG, MP, OBJ, false, LAY> t;
-  t.init(&lds[team].v, &tile, m, &p);
-  if (OBJ && t.tl < 4) {
-    const float* fr = v.rb_forces ? v.rb_forces + ((size_t)(m->num_bodies + 2) * ac + m->num_bodies) * 3 : nullptr;
-    lds[team].v.oforce[t.tl] = t.tl < 3 ? (fr ? fr[t.tl] : 0.0f) : (v.rb_force_space == MG_LOCAL_SPACE ? 1.0f : 0.0f);
-  }
-  mg::wsync();
-  float* root = v.root_states + (size_t)13 * ROWS * ac;
-  t.load(root, v.dof_state + (size_t)2 * nd * ac, v.dof_actuation ? v.dof_actuation + (size_t)nd * ac : nullptr,
-         OBJ ? root + 13 : nullptr, v.dof_targets ? v.dof_targets + (size_t)nd * ac : nullptr);
-  t.hull_stage();
-  t.fk();
-  if constexpr (OBJ == MG_GT_ELLIPSOID) {
-    t.egg_stage();
-    t.reload_tree();
-  }
-  t.set_axis();
-  if (OBJ) t.tendons();
-  t.aba();
-  t.obj_free();
-  t.collide();  // ends with a wave sync: s->ncon and the list are visible to the team
-  if (valid) {
-    auto& L = lds[team].v;
-    const int nc = L.ncon;
-    if (t.tl == 0) count[a] = nc;
-    for (int c = t.tl; c < nc && c < cap; c += T) {
-      float* o = out + ((size_t)a * cap + c) * 11;
-      o[0] = (float)t.cside(c, 0);
-      o[1] = (float)t.cside(c, 2);
-      o[2] = (float)t.cside(c, 1);
-      o[3] = (float)t.cside(c, 3);
-      for (int k = 0; k < 3; k++) {
-        o[4 + k] = L.cp[c][k];
-        o[7 + k] = L.cn[c][k];
-      }
-      o[10] = L.gap(c);
-    }
-  }
+  constexpr int E = Shape<T, MN, MC, MG, MP, OBJ, false, LAY>::E;
+  using TM = mg::Team<T, MN, MC, MG, MP, OBJ, false, LAY>;
+  __shared__ mg::BankSlot<typename TM::L, T> lds[E];
+  __shared__ typename TM::MT tile;
+  const TeamSlot k = team_enter<T, E>(&tile, timg, m, n);
+  TM t;
+  t.init(&lds[k.team].v, &tile, m, &p);
+  stage_object_force(t, v, k);
+  load_actor(t, v, k);
+  contacts_actor(t, k, out, count, cap);
+}
+
+// mg_debug_contacts while a heightfield is set (tests only): k_contacts for k_simulate_hf
+template <int T, int MN, int MC, int MG, int MP>
+__global__ __launch_bounds__((Shape<T, MN, MC, MG, MP, 0, false, 0>::kThreads)) __attribute__((amdgpu_waves_per_eu(Shape<T, MN, MC, MG, MP, 0, false, 0>::kWPE))) void k_contacts_hf(
+    const mg_model* __restrict__ m, const void* __restrict__ timg, mg_sim_params p, mg_state_views v, int n, mg::HfDesc hf,
+    const float* __restrict__ env_origins, float* __restrict__ out, int* __restrict__ count, int cap) {
+  constexpr int E = Shape<T, MN, MC, MG, MP, 0, false, 0>::E;
+  using TM = mg::Team<T, MN, MC, MG, MP, 0, false, 0, false, true>;
+  __shared__ mg::BankSlot<typename TM::L, T> lds[E];
+  __shared__ typename TM::MT tile;
+  const TeamSlot k = team_enter<T, E>(&tile, timg, m, n);
+  TM t;
+  t.init(&lds[k.team].v, &tile, m, &p);
+  t.bind_hf(hf, env_origins ? env_origins + (size_t)3 * k.ac : nullptr);
+  load_actor(t, v, k);
+  contacts_actor(t, k, out, count, cap);
 }
 
 // The whole VecTask.step for one actor, fused: clamp -> actuation -> simulate -> post_physics.
@@ -1216,42 +1182,58 @@ int BuildTile<T, MN, MC, MG, MP, OBJ, LAY>::run(mg_sim* sim) {
   return rc;
 }
 
+// run-time booleans as compile-time flags: with_flags(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}),
+// so a launcher names its kernel and its launch line once and the flags pick the instance
+template <class F>
+static int with_flags(F f) {
+  return f();
+}
+template <class F, class... B>
+static int with_flags(F f, bool b, B... rest) {
+  auto bound = [&](auto c) { return with_flags([&](auto... cs) { return f(c, cs...); }, rest...); };
+  return b ? bound(std::true_type{}) : bound(std::false_type{});
+}
+static bool solver_tgs(const mg_sim* sim) { return sim->params.solver_type == MG_SOLVER_TGS; }
+
+// every launcher's first check: `fn` is the entry point the error names
+static int check_tile(const mg_sim* sim, const char* fn) {
+  if (!sim->d_tile) return fail(MG_ECAPACITY, std::string(fn) + ": no model tile (model exceeds every kernel instance)");
+  return MG_OK;
+}
+// the contact read-outs': cap rows per actor hold the most contacts the kernel's collide() keeps for one
+template <int MC>
+static int check_contact_cap(const mg_sim* sim, int32_t cap) {
+  const int kept = sim->params.max_contacts < MC ? sim->params.max_contacts : MC;
+  if (cap < kept) return fail(MG_EINVAL, "mg_debug_contacts: cap is below the kernel's contact count");
+  return MG_OK;
+}
+
 template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY>
 int RunSimulate<T, MN, MC, MG, MP, OBJ, LAY>::run(hipStream_t s, const mg_sim* sim) {
-  if (!sim->d_tile) return fail(MG_ECAPACITY, "mg_sim_simulate: no model tile (model exceeds every kernel instance)");
+  if (const int rc = check_tile(sim, "mg_sim_simulate")) return rc;
   // the domain-randomized instance reads each actor's env_props row (mg_dr_apply); TGS runs its own instances
-  const bool tgs = sim->params.solver_type == MG_SOLVER_TGS;
-  if (sim->views.env_props) {
-    if (tgs)
-      launch<Shape<T, MN, MC, MG, MP, OBJ, true, LAY>>(k_simulate<T, MN, MC, MG, MP, OBJ, true, true, LAY>, s, sim->n, sim->d_model,
-                                                   (const void*)sim->d_tile, sim->params, sim->views, sim->n);
-    else
-      launch<Shape<T, MN, MC, MG, MP, OBJ, true, LAY>>(k_simulate<T, MN, MC, MG, MP, OBJ, true, false, LAY>, s, sim->n, sim->d_model,
-                                                   (const void*)sim->d_tile, sim->params, sim->views, sim->n);
-  } else if (tgs) {
-    launch<Shape<T, MN, MC, MG, MP, OBJ, false, LAY>>(k_simulate<T, MN, MC, MG, MP, OBJ, false, true, LAY>, s, sim->n, sim->d_model,
-                                                  (const void*)sim->d_tile, sim->params, sim->views, sim->n);
-  } else {
-    launch<Shape<T, MN, MC, MG, MP, OBJ, false, LAY>>(k_simulate<T, MN, MC, MG, MP, OBJ, false, false, LAY>, s, sim->n, sim->d_model,
-                                                  (const void*)sim->d_tile, sim->params, sim->views, sim->n);
-  }
-  return MG_OK;
+  return with_flags(
+      [&](auto dr, auto tgs) {
+        launch<Shape<T, MN, MC, MG, MP, OBJ, dr(), LAY>>(k_simulate<T, MN, MC, MG, MP, OBJ, dr(), tgs(), LAY>, s, sim->n,
+                                                         sim->d_model, (const void*)sim->d_tile, sim->params, sim->views, sim->n);
+        return MG_OK;
+      },
+      sim->views.env_props != nullptr, solver_tgs(sim));
 }
 
 template <int T, int MN, int MC, int MG, int MP>
 int RunSimulateXF<T, MN, MC, MG, MP>::run(hipStream_t s, const mg_sim* sim) {
-  if (!sim->d_tile) return fail(MG_ECAPACITY, "mg_sim_simulate: no model tile (model exceeds every kernel instance)");
+  if (const int rc = check_tile(sim, "mg_sim_simulate")) return rc;
   // one LDS row and one lane per body (Team::bind_xf)
   if (sim->host_model.num_bodies > MN)
     return fail(MG_ECAPACITY, "mg_sim_simulate: link forces: the model has more bodies than its kernel instance has nodes");
-  using SH = Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>;
-  if (sim->params.solver_type == MG_SOLVER_TGS)
-    launch<SH>(k_simulate_xf<T, MN, MC, MG, MP, true>, s, sim->n, sim->d_model, (const void*)sim->d_tile, sim->params,
-               sim->views, sim->n);
-  else
-    launch<SH>(k_simulate_xf<T, MN, MC, MG, MP, false>, s, sim->n, sim->d_model, (const void*)sim->d_tile, sim->params,
-               sim->views, sim->n);
-  return MG_OK;
+  return with_flags(
+      [&](auto tgs) {
+        launch<Shape<T, MN, MC, MG, MP, 0, false, 0, 24 * MN>>(k_simulate_xf<T, MN, MC, MG, MP, tgs()>, s, sim->n, sim->d_model,
+                                                               (const void*)sim->d_tile, sim->params, sim->views, sim->n);
+        return MG_OK;
+      },
+      solver_tgs(sim));
 }
 
 // the kernels' descriptor of the field the sim has set
@@ -1262,22 +1244,21 @@ static mg::HfDesc hf_desc(const mg_heightfield& f) {
 
 template <int T, int MN, int MC, int MG, int MP>
 int RunSimulateHF<T, MN, MC, MG, MP>::run(hipStream_t s, const mg_sim* sim) {
-  if (!sim->d_tile) return fail(MG_ECAPACITY, "mg_sim_simulate: no model tile (model exceeds every kernel instance)");
-  using SH = Shape<T, MN, MC, MG, MP, 0, false, 0>;
-  if (sim->params.solver_type == MG_SOLVER_TGS)
-    launch<SH>(k_simulate_hf<T, MN, MC, MG, MP, true>, s, sim->n, sim->d_model, (const void*)sim->d_tile, sim->params,
-               sim->views, sim->n, hf_desc(sim->hf), sim->hf.env_origins);
-  else
-    launch<SH>(k_simulate_hf<T, MN, MC, MG, MP, false>, s, sim->n, sim->d_model, (const void*)sim->d_tile, sim->params,
-               sim->views, sim->n, hf_desc(sim->hf), sim->hf.env_origins);
-  return MG_OK;
+  if (const int rc = check_tile(sim, "mg_sim_simulate")) return rc;
+  return with_flags(
+      [&](auto tgs) {
+        launch<Shape<T, MN, MC, MG, MP, 0, false, 0>>(k_simulate_hf<T, MN, MC, MG, MP, tgs()>, s, sim->n, sim->d_model,
+                                                      (const void*)sim->d_tile, sim->params, sim->views, sim->n,
+                                                      hf_desc(sim->hf), sim->hf.env_origins);
+        return MG_OK;
+      },
+      solver_tgs(sim));
 }
 
 template <int T, int MN, int MC, int MG, int MP>
 int RunContactsHF<T, MN, MC, MG, MP>::run(hipStream_t s, const mg_sim* sim, float* out, int32_t* count, int32_t cap) {
-  if (!sim->d_tile) return fail(MG_ECAPACITY, "mg_debug_contacts: no model tile (model exceeds every kernel instance)");
-  const int kept = sim->params.max_contacts < MC ? sim->params.max_contacts : MC;
-  if (cap < kept) return fail(MG_EINVAL, "mg_debug_contacts: cap is below the kernel's contact count");
+  if (const int rc = check_tile(sim, "mg_debug_contacts")) return rc;
+  if (const int rc = check_contact_cap<MC>(sim, cap)) return rc;
   launch<Shape<T, MN, MC, MG, MP, 0, false, 0>>(k_contacts_hf<T, MN, MC, MG, MP>, s, sim->n, sim->d_model,
                                                 (const void*)sim->d_tile, sim->params, sim->views, sim->n, hf_desc(sim->hf),
                                                 sim->hf.env_origins, out, count, (int)cap);
@@ -1286,10 +1267,8 @@ int RunContactsHF<T, MN, MC, MG, MP>::run(hipStream_t s, const mg_sim* sim, floa
 
 template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY>
 int RunContacts<T, MN, MC, MG, MP, OBJ, LAY>::run(hipStream_t s, const mg_sim* sim, float* out, int32_t* count, int32_t cap) {
-  if (!sim->d_tile) return fail(MG_ECAPACITY, "mg_debug_contacts: no model tile (model exceeds every kernel instance)");
-  // the most contacts the kernel's collide() keeps for an actor
-  const int kept = sim->params.max_contacts < MC ? sim->params.max_contacts : MC;
-  if (cap < kept) return fail(MG_EINVAL, "mg_debug_contacts: cap is below the kernel's contact count");
+  if (const int rc = check_tile(sim, "mg_debug_contacts")) return rc;
+  if (const int rc = check_contact_cap<MC>(sim, cap)) return rc;
   launch<Shape<T, MN, MC, MG, MP, OBJ, false, LAY>>(k_contacts<T, MN, MC, MG, MP, OBJ, LAY>, s, sim->n, sim->d_model,
                                                     (const void*)sim->d_tile, sim->params, sim->views, sim->n, out, count,
                                                     (int)cap);
@@ -1300,7 +1279,7 @@ template <int T, int MN, int MC, int MG, int MP, int OBJ, int LAY>
 int RunEnvStep<T, MN, MC, MG, MP, OBJ, LAY>::run(hipStream_t s, const mg_sim* sim, const mg_task_params* tp,
                                                   const mg_task_buffers* tb, const mg_replay* rp) {
   using TL = mg::TeamLDSOf<T, MN, MC, OBJ, MG, MP, LAY>;
-  if (!sim->d_tile) return fail(MG_ECAPACITY, "mg_env_step: no model tile (model exceeds every kernel instance)");
+  if (const int rc = check_tile(sim, "mg_env_step")) return rc;
   // observations are staged in the (dead) row storage of the team's LDS before the coalesced store
   if (!OBJ && (size_t)tp->num_obs * sizeof(float) > TL::kObsStageBytes)
     return fail(MG_ECAPACITY, "mg_env_step: observation row exceeds the kernel's staging area");
@@ -1316,43 +1295,30 @@ int RunEnvStep<T, MN, MC, MG, MP, OBJ, LAY>::run(hipStream_t s, const mg_sim* si
     return fail(MG_EINVAL, "mg_env_step_replay: no replay instance with domain randomization");
   const mg_replay r = rp ? *rp : mg_replay{};
   const void* ti = sim->d_tile;
-  const bool tgs = sim->params.solver_type == MG_SOLVER_TGS;  // TGS runs its own instances (not the replay's: no physics)
+  // the replay instance (no physics: neither DR nor TGS, and no work ordering) first; then TGS and DR run their own
   if constexpr (OBJ != 0) {
     mg_task_params tpm = *tp;  // observation column maps (hand_task.hpp h_fill_maps)
     mg::h_fill_maps(&tpm);
     if (rp)
       return launch_wq<Shape<T, MN, MC, MG, MP, OBJ, false>>(k_hand_step<T, MN, MC, MG, MP, OBJ, false, true>, s, sim, false,
                                                     sim->d_model, ti, sim->params, tpm, sim->views, *tb, sim->n, r);
-    else if (sim->views.env_props && tgs)
-      return launch_wq<Shape<T, MN, MC, MG, MP, OBJ, true>>(k_hand_step<T, MN, MC, MG, MP, OBJ, true, false, true>, s, sim,
-                                                   true, sim->d_model, ti, sim->params, tpm, sim->views, *tb, sim->n, r);
-    else if (sim->views.env_props)
-      return launch_wq<Shape<T, MN, MC, MG, MP, OBJ, true>>(k_hand_step<T, MN, MC, MG, MP, OBJ, true, false>, s, sim, true,
-                                                   sim->d_model, ti, sim->params, tpm, sim->views, *tb, sim->n, r);
-    else if (tgs)
-      return launch_wq<Shape<T, MN, MC, MG, MP, OBJ, false>>(k_hand_step<T, MN, MC, MG, MP, OBJ, false, false, true>, s, sim,
-                                                    true, sim->d_model, ti, sim->params, tpm, sim->views, *tb, sim->n, r);
-    else
-      return launch_wq<Shape<T, MN, MC, MG, MP, OBJ, false>>(k_hand_step<T, MN, MC, MG, MP, OBJ, false, false>, s, sim, true,
-                                                    sim->d_model, ti, sim->params, tpm, sim->views, *tb, sim->n, r);
+    return with_flags(
+        [&](auto dr, auto tgs) {
+          return launch_wq<Shape<T, MN, MC, MG, MP, OBJ, dr()>>(k_hand_step<T, MN, MC, MG, MP, OBJ, dr(), false, tgs()>, s, sim,
+                                                                true, sim->d_model, ti, sim->params, tpm, sim->views, *tb, sim->n, r);
+        },
+        sim->views.env_props != nullptr, solver_tgs(sim));
   } else {
     if (rp)
       return launch_wq<Shape<T, MN, MC, MG, MP, 0, false, LAY>>(k_env_step<T, MN, MC, MG, MP, false, true, false, LAY>, s, sim, false, sim->d_model,
                                                   ti, sim->params, *tp, sim->views, *tb, sim->n, r);
-    else if (sim->views.env_props && tgs)
-      return launch_wq<Shape<T, MN, MC, MG, MP, 0, true, LAY>>(k_env_step<T, MN, MC, MG, MP, true, false, true, LAY>, s, sim, true,
-                                                 sim->d_model, ti, sim->params, *tp, sim->views, *tb, sim->n, r);
-    else if (sim->views.env_props)
-      return launch_wq<Shape<T, MN, MC, MG, MP, 0, true, LAY>>(k_env_step<T, MN, MC, MG, MP, true, false, false, LAY>, s, sim, true, sim->d_model,
-                                                 ti, sim->params, *tp, sim->views, *tb, sim->n, r);
-    else if (tgs)
-      return launch_wq<Shape<T, MN, MC, MG, MP, 0, false, LAY>>(k_env_step<T, MN, MC, MG, MP, false, false, true, LAY>, s, sim, true,
-                                                  sim->d_model, ti, sim->params, *tp, sim->views, *tb, sim->n, r);
-    else
-      return launch_wq<Shape<T, MN, MC, MG, MP, 0, false, LAY>>(k_env_step<T, MN, MC, MG, MP, false, false, false, LAY>, s, sim, true, sim->d_model,
-                                                  ti, sim->params, *tp, sim->views, *tb, sim->n, r);
+    return with_flags(
+        [&](auto dr, auto tgs) {
+          return launch_wq<Shape<T, MN, MC, MG, MP, 0, dr(), LAY>>(k_env_step<T, MN, MC, MG, MP, dr(), false, tgs(), LAY>, s, sim,
+                                                                   true, sim->d_model, ti, sim->params, *tp, sim->views, *tb, sim->n, r);
+        },
+        sim->views.env_props != nullptr, solver_tgs(sim));
   }
-  return MG_OK;
 }
 
 template <int I>

@@ -945,6 +945,7 @@ struct Team : TeamXf<XF>, TeamHf<HF> {
   using L = TeamLDSOf<T, MN, MC, OBJ, MG, MP, LAY>;
   using MT = ModelTile<MN, MG, MP, tile_hull_verts(OBJ)>;
   static constexpr int MR = L::MR;
+  static constexpr int kT = T, kObj = OBJ;
   // the hardware sine / cosine for the 16-lane teams (Ant, MA-Ant), poly_sincos elsewhere (device_math.hpp psincos)
   static constexpr bool kHwTrig = T == 16 && OBJ == 0;
   // the root's child sum over the team's lanes (aba()): the 16-lane compact teams
@@ -2721,8 +2722,9 @@ struct Team : TeamXf<XF>, TeamHf<HF> {
   }
 
   // ---------------------------------------------------------------- one substep
-  // (step_kernels.hpp k_contacts repeats the sequence below up to collide(), less root_coupling(), which writes
-  // nothing collide() reads: change both together)
+  // (step_kernels.hpp contacts_actor(), the body of both contact read-outs, repeats the sequence below up to
+  // collide(), less root_coupling(), which writes nothing collide() reads: change both together.  A member shared
+  // with substep() moved the step kernels' instruction schedule, so the copy stays, once)
   __device__ __forceinline__ void substep() {
     ph_mark(15);
     hull_stage();

@@ -28,7 +28,7 @@ for line in out.splitlines():
 keys = ["VGPRs", "AGPRs", "VGPRs Spill", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]"]
 print(f"{'kernel':70s} " + " ".join(f"{k.split()[0]:>9s}" for k in keys))
 for r in rows:
-    if not re.search(r"k_(env_step|hand_step|simulate)", r["name"]):
+    if not re.search(r"k_(env_step|hand_step|simulate|contacts)", r["name"]):
         continue
     m = re.match(r"_Z\d+(k_\w+?)I(.*?)E(?:E|v)", r["name"])
     n = m.group(1) + "<" + ",".join(re.findall(r"L[ib](\d+)E", m.group(2) + "E")) + ">" if m else r["name"]
