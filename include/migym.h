@@ -956,6 +956,105 @@ int mg_amp_reset_idx(mg_sim* sim, const mg_amp_params* ap, const mg_amp_views* v
 int mg_amp_obs_demo(const mg_amp_params* ap, const mg_amp_views* views, const float* noise, uint64_t seed,
                     uint64_t counter, float* out, int32_t num_samples, void* stream);
 
+/* ---- AnymalTerrain (anymal_terrain.py): rough-terrain locomotion with a terrain curriculum.  A control step is
+ * (mg_anymal_terrain_pre, mg_sim_simulate) x decimation, then mg_anymal_terrain_post (one launch over the envs and
+ * one small finishing launch for the cross-env means), all asynchronous on the caller's stream, no host
+ * synchronisation, no floating-point atomics.  One free-base 12-DOF articulation per env in effort mode; the sim must
+ * have dof_actuation and net_contact_forces bound, and root_states in world coordinates (the heightfield set without
+ * per-actor origins).  New structs only. */
+#define MG_ANYMAL_TERRAIN_OBS 188
+#define MG_ANYMAL_TERRAIN_HEIGHT_POINTS 140
+#define MG_ANYMAL_TERRAIN_NOISE_COLS 219
+#define MG_ANYMAL_TERRAIN_REWARDS 13
+typedef struct mg_anymal_terrain_params {
+  /* learn.*Scale (anymal_terrain.py:54-58) */
+  float lin_vel_scale, ang_vel_scale, dof_pos_scale, dof_vel_scale, height_meas_scale;
+  /* learn.*RewardScale * dt, dt = decimation * sim.dt, the product taken in double on the host and rounded to fp32
+   * once (anymal_terrain.py:104-105), in the order of episode_sums: lin_vel_xy, lin_vel_z, ang_vel_z, ang_vel_xy,
+   * orient, torques, joint_acc, base_height, air_time, collision, stumble, action_rate, hip */
+  float rew_scale[MG_ANYMAL_TERRAIN_REWARDS];
+  float rew_termination;              /* terminalReward * dt */
+  float dt;                           /* what feet_air_time advances by per control step: sim.dt, not decimation *
+                                       * sim.dt -- VecTask.__init__ overwrites the task's self.dt (vec_task.py:242) */
+  float Kp, Kd, action_scale, torque_clip;   /* control.stiffness, damping, actionScale; 80 */
+  float default_dof_pos[MG_ANYMAL_DOFS];
+  float base_init_state[13];
+  float command_lo[3], command_span[3];      /* linear_x, linear_y, heading (the YAML's yaw): span = hi - lo in double */
+  int32_t base_body, knee_body[4], foot_body[4];   /* net_contact_forces rows */
+  int32_t hip_dof[4];                 /* the DOF columns of the hip penalty (0, 3, 6, 9) */
+  int32_t num_bodies;
+  int32_t allow_knee_contacts, add_noise;
+  float noise_scale_vec[MG_ANYMAL_TERRAIN_OBS];
+  int32_t max_episode_length;         /* int(episodeLength_s / dt + 0.5) */
+  float max_episode_length_s;
+  float env_length;                   /* terrain.mapLength: an env climbs a level past env_length / 2 */
+  int32_t env_rows, env_cols;         /* numLevels, numTerrains: the shape of terrain_origins */
+  int32_t curriculum, custom_origins;
+  /* the height scan's field, mg_height_scan's rule: heights[i * ny + j] in metres (vertical_scale applied) at world
+   * (x0 + i dx, y0 + j dx); NULL (terrainType plane): every height 0 */
+  const float* hf_heights;
+  int32_t hf_nx, hf_ny;
+  float hf_dx, hf_x0, hf_y0;
+  float height_points[2 * MG_ANYMAL_TERRAIN_HEIGHT_POINTS];   /* (x, y) in the base's yaw frame */
+  float clip_actions, clip_obs;
+  int32_t pad_atp;
+} mg_anymal_terrain_params;
+
+/* task-owned device tensors */
+typedef struct mg_anymal_terrain_views {
+  float* commands;                    /* (N, 4) [x, y, yaw rate, heading] */
+  float* torques;                     /* (N, 12) the last substep's PD torques */
+  float* last_actions;                /* (N, 12) */
+  float* last_dof_vel;                /* (N, 12) */
+  float* feet_air_time;               /* (N, 4) */
+  float* episode_sums;                /* (N, 13), columns as rew_scale */
+  int32_t* terrain_levels;            /* (N) */
+  const int32_t* terrain_types;       /* (N) */
+  float* env_origins;                 /* (N, 3) */
+  const float* terrain_origins;       /* (env_rows, env_cols, 3) */
+  float* dof_actuation;               /* (N*12): the buffer the sim has bound as dof_actuation */
+  float* episode_out;                 /* (14): 13 means / max_episode_length_s and the mean terrain level; written only
+                                       * by a launch in which at least one env reset */
+  float* measured_heights;            /* (N, 140) get_heights as the observations took it, or NULL */
+  float* partials;                    /* (ceil(N / 4), 16) scratch of the two-stage means */
+  int32_t* reset_mark;                /* (N) scratch of mg_anymal_terrain_reset_idx, all zero between calls */
+  int32_t push_now;                   /* set by the host per step: push_robots runs in this post */
+  int32_t pad_atv;
+} mg_anymal_terrain_views;
+size_t mg_anymal_terrain_params_sizeof(void);
+size_t mg_anymal_terrain_views_sizeof(void);
+
+/* mg_task_buffers fields these entry points use: actions (N, 12), actions_out, obs (N, 188), obs_clamped, rew, reset,
+ * progress, timeout, noise, seed, step_counter, env_offset, out_pack.  noise: (N, 219) U(0,1) per env in the
+ * reference's draw order [push vx vy 2 | positions_offset 12 | velocities 12 | root x y 2 | command x | y | heading |
+ * observation noise 188]; NULL = the counter RNG keyed by (seed, env_offset + env, step_counter, column). */
+
+/* The explicit PD torque of one decimation step (anymal_terrain.py:443-447), one lane per (env, DOF): a =
+ * clamp(actions, +-clip_actions) -> actions_out; torque = clip(Kp * (action_scale * a + default - dof_pos) - Kd *
+ * dof_vel, +-torque_clip) in the reference's operation order, no FMA -> the bound dof_actuation and views.torques.
+ * Launched before every mg_sim_simulate of a control step. */
+int mg_anymal_terrain_pre(mg_sim* sim, const mg_anymal_terrain_params* ap, const mg_anymal_terrain_views* views,
+                          const mg_task_buffers* tb, void* stream);
+
+/* post_physics_step + the VecTask.step tail (anymal_terrain.py:453-485, 294-436), per env and in the reference's
+ * order: progress += 1; the push (views.push_now); base velocities, projected gravity, heading and commands[2] from the
+ * root row; check_termination; compute_reward (timeout read as the previous step left it); the envs whose reset flag
+ * was just set are reset in the same launch (curriculum by the per-env command norm, DOF draws, root row at the env
+ * origin, new commands); observations (base-frame columns stale for a reset env, as in the reference), noise,
+ * last_actions, last_dof_vel; timeout, the observation clamp, out_pack.  Then the finishing launch writes episode_out
+ * if any env reset.  state: NULL = the sim's bound views; else its root_states, dof_state and net_contact_forces are
+ * taken as the post-simulate state (root_states and dof_state are written by a push or a reset). */
+int mg_anymal_terrain_post(mg_sim* sim, const mg_anymal_terrain_params* ap, const mg_anymal_terrain_views* views,
+                           const mg_task_buffers* tb, const mg_state_views* state, void* stream);
+
+/* reset_idx(env_ids) now (anymal_terrain.py:384-425): the listed envs get the reset of mg_anymal_terrain_post,
+ * last_actions = last_dof_vel = 0, progress = 0 and reset = 1; update_levels != 0 runs update_terrain_level first (0:
+ * the constructor's reset, the reference's init_done).  A repeated id is harmless, an id outside 0..N-1 is skipped.
+ * Noise: tb->noise rows by env, or the counter RNG on the manual-reset stream (step_counter | 2^62). */
+int mg_anymal_terrain_reset_idx(mg_sim* sim, const mg_anymal_terrain_params* ap,
+                                const mg_anymal_terrain_views* views, const mg_task_buffers* tb, const int32_t* ids,
+                                int32_t n, int32_t update_levels, void* stream);
+
 /* Measurement aid (no reference counterpart; bench.py's roofline.kernel_ms): the device-side duration of the
  * fused step kernel, from the first wave's start to the last wave's end on the GPU's constant wall clock
  * (wall_clock64, hipDeviceAttributeWallClockRate), so that no launch, queue or event-packet overhead is in it.

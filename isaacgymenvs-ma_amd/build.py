@@ -9,6 +9,7 @@
     hipcc ... -c csrc/inst.hip -DMG_INST=i -DMG_HEIGHTFIELD_TU    (k_simulate on heightfield terrain and its contact
                                                                     read-out: the same instances)
     hipcc -O3 --offload-arch=gfx950 -c csrc/height_scan.hip       (mg_height_scan's kernel)
+    hipcc -O3 --offload-arch=gfx950 -c csrc/anymal_terrain.hip    (AnymalTerrain's kernels and entry points)
     hipcc -shared *.o -> migym/_lib/libmigym.so
 
 The objects compile in parallel (one process per translation unit, at most MIGYM_JOBS / os.cpu_count()).
@@ -27,6 +28,7 @@ CSRC = os.path.join(HERE, "csrc")
 SRC = os.path.join(CSRC, "migym.hip")
 INST = os.path.join(CSRC, "inst.hip")
 SCAN = os.path.join(CSRC, "height_scan.hip")
+TERRAIN = os.path.join(CSRC, "anymal_terrain.hip")
 OUT = os.path.join(HERE, "migym", "_lib", "libmigym.so")
 OUT_TIMING = os.path.join(HERE, "migym", "_lib", "libmigym_timing.so")
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "migym.h")]
@@ -51,7 +53,7 @@ def needs_build(out=OUT):
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
-    return any(os.path.getmtime(p) > t for p in [SRC, INST, SCAN, __file__] + HEADERS)
+    return any(os.path.getmtime(p) > t for p in [SRC, INST, SCAN, TERRAIN, __file__] + HEADERS)
 
 
 def _run_parallel(cmds, verbose):
@@ -121,6 +123,7 @@ def build(force=False, verbose=False, timing=False, variant=None, defines=(), ex
         for i in instances:
             unit(f"{prefix}{i}", INST, f"-DMG_INST={i}", *inst_flags, *(["-D" + define] if define else []))
     unit("height_scan", SCAN)  # mg_height_scan's kernel
+    unit("anymal_terrain", TERRAIN)  # mg_anymal_terrain_*: linked last, the code objects before it stay as they are
     _run_parallel(cmds, verbose)
     subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out + ".tmp"] + objs)
     sys.path.insert(0, HERE)

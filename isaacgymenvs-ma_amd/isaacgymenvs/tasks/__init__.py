@@ -1,2 +1,2 @@
 from migym.tasks import isaacgym_task_map, Ant, Humanoid, Cartpole, FrankaReachMA, Anymal, \
-    HumanoidAMP, Quadcopter  # noqa: F401
+    HumanoidAMP, Quadcopter, AnymalTerrain  # noqa: F401

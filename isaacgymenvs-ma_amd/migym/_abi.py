@@ -179,6 +179,42 @@ class AnymalViews(C.Structure):
     _fields_ = [("commands", C.c_void_p), ("dof_targets", C.c_void_p)]
 
 
+MG_ANYMAL_TERRAIN_OBS, MG_ANYMAL_TERRAIN_HEIGHT_POINTS, MG_ANYMAL_TERRAIN_NOISE_COLS = 188, 140, 219
+MG_ANYMAL_TERRAIN_REWARDS = 13
+# the columns of rew_scale, episode_sums and episode_out: the keys of the reference's episode_sums, in its order
+ANYMAL_TERRAIN_REWARDS = ("lin_vel_xy", "lin_vel_z", "ang_vel_z", "ang_vel_xy", "orient", "torques", "joint_acc",
+                          "base_height", "air_time", "collision", "stumble", "action_rate", "hip")
+
+
+class AnymalTerrainParams(C.Structure):
+    """mg_anymal_terrain_params: the constants of AnymalTerrain (taskdefs.anymal_terrain_params)."""
+    _fields_ = [("lin_vel_scale", C.c_float), ("ang_vel_scale", C.c_float), ("dof_pos_scale", C.c_float),
+                ("dof_vel_scale", C.c_float), ("height_meas_scale", C.c_float),
+                ("rew_scale", C.c_float * MG_ANYMAL_TERRAIN_REWARDS), ("rew_termination", C.c_float),
+                ("dt", C.c_float), ("Kp", C.c_float), ("Kd", C.c_float), ("action_scale", C.c_float),
+                ("torque_clip", C.c_float), ("default_dof_pos", C.c_float * MG_ANYMAL_DOFS),
+                ("base_init_state", C.c_float * 13), ("command_lo", C.c_float * 3), ("command_span", C.c_float * 3),
+                ("base_body", C.c_int32), ("knee_body", C.c_int32 * 4), ("foot_body", C.c_int32 * 4),
+                ("hip_dof", C.c_int32 * 4), ("num_bodies", C.c_int32), ("allow_knee_contacts", C.c_int32),
+                ("add_noise", C.c_int32), ("noise_scale_vec", C.c_float * MG_ANYMAL_TERRAIN_OBS),
+                ("max_episode_length", C.c_int32), ("max_episode_length_s", C.c_float), ("env_length", C.c_float),
+                ("env_rows", C.c_int32), ("env_cols", C.c_int32), ("curriculum", C.c_int32),
+                ("custom_origins", C.c_int32), ("hf_heights", C.c_void_p), ("hf_nx", C.c_int32), ("hf_ny", C.c_int32),
+                ("hf_dx", C.c_float), ("hf_x0", C.c_float), ("hf_y0", C.c_float),
+                ("height_points", C.c_float * (2 * MG_ANYMAL_TERRAIN_HEIGHT_POINTS)), ("clip_actions", C.c_float),
+                ("clip_obs", C.c_float), ("pad_atp", C.c_int32)]
+
+
+class AnymalTerrainViews(C.Structure):
+    """mg_anymal_terrain_views: the task-owned device tensors of AnymalTerrain."""
+    _fields_ = [("commands", C.c_void_p), ("torques", C.c_void_p), ("last_actions", C.c_void_p),
+                ("last_dof_vel", C.c_void_p), ("feet_air_time", C.c_void_p), ("episode_sums", C.c_void_p),
+                ("terrain_levels", C.c_void_p), ("terrain_types", C.c_void_p), ("env_origins", C.c_void_p),
+                ("terrain_origins", C.c_void_p), ("dof_actuation", C.c_void_p), ("episode_out", C.c_void_p),
+                ("measured_heights", C.c_void_p), ("partials", C.c_void_p), ("reset_mark", C.c_void_p),
+                ("push_now", C.c_int32), ("pad_atv", C.c_int32)]
+
+
 class Heightfield(C.Structure):
     """mg_heightfield: the terrain table of mg_sim_set_heightfield (device pointers, kept by the sim, not copied)."""
     _fields_ = [("heights", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("dx", C.c_float), ("x0", C.c_float),
@@ -316,6 +352,15 @@ EXPORTS = {
                                  C.POINTER(StateViews), C.c_void_p]),
     "mg_anymal_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(AnymalParams), C.POINTER(AnymalViews),
                                       C.POINTER(TaskBuffers), C.c_void_p, C.c_int32, C.c_void_p]),
+    "mg_anymal_terrain_params_sizeof": (C.c_size_t, []),
+    "mg_anymal_terrain_views_sizeof": (C.c_size_t, []),
+    "mg_anymal_terrain_pre": (C.c_int, [C.c_void_p, C.POINTER(AnymalTerrainParams), C.POINTER(AnymalTerrainViews),
+                                        C.POINTER(TaskBuffers), C.c_void_p]),
+    "mg_anymal_terrain_post": (C.c_int, [C.c_void_p, C.POINTER(AnymalTerrainParams), C.POINTER(AnymalTerrainViews),
+                                         C.POINTER(TaskBuffers), C.POINTER(StateViews), C.c_void_p]),
+    "mg_anymal_terrain_reset_idx": (C.c_int, [C.c_void_p, C.POINTER(AnymalTerrainParams),
+                                              C.POINTER(AnymalTerrainViews), C.POINTER(TaskBuffers), C.c_void_p,
+                                              C.c_int32, C.c_int32, C.c_void_p]),
     "mg_quadcopter_params_sizeof": (C.c_size_t, []),
     "mg_quadcopter_views_sizeof": (C.c_size_t, []),
     "mg_quadcopter_pre": (C.c_int, [C.c_void_p, C.POINTER(QuadcopterParams), C.POINTER(QuadcopterViews),
@@ -365,7 +410,9 @@ def check_layout(lib):
              "mg_amp_params_sizeof": C.sizeof(AmpParams), "mg_amp_views_sizeof": C.sizeof(AmpViews),
              "mg_quadcopter_params_sizeof": C.sizeof(QuadcopterParams),
              "mg_quadcopter_views_sizeof": C.sizeof(QuadcopterViews),
-             "mg_heightfield_sizeof": C.sizeof(Heightfield)}
+             "mg_heightfield_sizeof": C.sizeof(Heightfield),
+             "mg_anymal_terrain_params_sizeof": C.sizeof(AnymalTerrainParams),
+             "mg_anymal_terrain_views_sizeof": C.sizeof(AnymalTerrainViews)}
     for fn, py in sizes.items():
         c = getattr(lib, fn)()
         if c != py:

@@ -280,6 +280,47 @@ TASKS["Anymal"] = {
 }
 
 
+# AnymalTerrain (cfg/task/AnymalTerrain.yaml): only the keys the task reads.  The model is found as Anymal's is:
+# env.asset.modelTable names a JSON model table (tools/build_models.py anymal_minimal writes one), or assetRoot +
+# assetFileName the URDF.  frictionRange is kept for the record: per-env friction is not built.
+TASKS["AnymalTerrain"] = {
+    "name": "AnymalTerrain",
+    "env": {
+        # no clipObservations / clipActions: the reference's YAML has neither, so VecTask clips at infinity
+        "numEnvs": 4096, "envSpacing": 3.0, "enableDebugVis": False,
+        "terrain": {"terrainType": "trimesh", "staticFriction": 1.0, "dynamicFriction": 1.0, "restitution": 0.0,
+                    "curriculum": True, "maxInitMapLevel": 0, "mapLength": 8.0, "mapWidth": 8.0, "numLevels": 10,
+                    "numTerrains": 20, "terrainProportions": [0.1, 0.1, 0.35, 0.25, 0.2], "slopeTreshold": 0.5},
+        "baseInitState": {"pos": [0.0, 0.0, 0.62], "rot": [0.0, 0.0, 0.0, 1.0], "vLinear": [0.0, 0.0, 0.0],
+                          "vAngular": [0.0, 0.0, 0.0]},
+        "randomCommandVelocityRanges": {"linear_x": [-1.0, 1.0], "linear_y": [-1.0, 1.0], "yaw": [-3.14, 3.14]},
+        "control": {"stiffness": 80.0, "damping": 2.0, "actionScale": 0.5, "decimation": 4},
+        "defaultJointAngles": {"LF_HAA": 0.03, "LH_HAA": 0.03, "RF_HAA": -0.03, "RH_HAA": -0.03,
+                               "LF_HFE": 0.4, "LH_HFE": -0.4, "RF_HFE": 0.4, "RH_HFE": -0.4,
+                               "LF_KFE": -0.8, "LH_KFE": 0.8, "RF_KFE": -0.8, "RH_KFE": 0.8},
+        "urdfAsset": {"file": "urdf/anymal_c/urdf/anymal_minimal.urdf", "footName": "SHANK", "kneeName": "THIGH",
+                      "collapseFixedJoints": True, "fixBaseLink": False, "defaultDofDriveMode": 4},
+        "learn": {"allowKneeContacts": True, "terminalReward": 0.0, "linearVelocityXYRewardScale": 1.0,
+                  "linearVelocityZRewardScale": -4.0, "angularVelocityXYRewardScale": -0.05,
+                  "angularVelocityZRewardScale": 0.5, "orientationRewardScale": -0.0, "torqueRewardScale": -0.00002,
+                  "jointAccRewardScale": -0.0005, "baseHeightRewardScale": -0.0, "feetAirTimeRewardScale": 1.0,
+                  "kneeCollisionRewardScale": -0.25, "feetStumbleRewardScale": -0.0, "actionRateRewardScale": -0.01,
+                  "hipRewardScale": -0.0, "linearVelocityScale": 2.0, "angularVelocityScale": 0.25,
+                  "dofPositionScale": 1.0, "dofVelocityScale": 0.05, "heightMeasurementScale": 5.0,
+                  "addNoise": True, "noiseLevel": 1.0, "dofPositionNoise": 0.01, "dofVelocityNoise": 1.5,
+                  "linearVelocityNoise": 0.1, "angularVelocityNoise": 0.2, "gravityNoise": 0.05,
+                  "heightMeasurementNoise": 0.06, "randomizeFriction": True, "frictionRange": [0.5, 1.25],
+                  "pushRobots": True, "pushInterval_s": 15, "episodeLength_s": 20},
+        "asset": {"assetRoot": "../../assets", "assetFileName": "urdf/anymal_c/urdf/anymal_minimal.urdf"},
+        "enableCameraSensors": False,
+    },
+    "sim": _sim(dt=0.005, num_position_iterations=4, num_velocity_iterations=1, contact_offset=0.02, rest_offset=0.0,
+                bounce_threshold_velocity=0.2, max_depenetration_velocity=100.0, contact_collection=1),
+    "task": {"randomize": False},
+}
+TASKS["AnymalTerrain"]["sim"]["substeps"] = 1
+
+
 # HumanoidAMP (cfg/task/HumanoidAMP.yaml): only the keys the task reads.  Neither the AMP humanoid nor a motion clip is
 # shipped: env.asset.modelTable names a JSON model table (tools/build_models.py amp_humanoid writes one), or assetRoot +
 # assetFileName the MJCF; env.motion_file names a clip (.npy / .npz / .yaml), absolute or under env.asset.motionRoot.

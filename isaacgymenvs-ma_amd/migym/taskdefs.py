@@ -544,3 +544,111 @@ def amp_params(cfg: dict, spec: M.ModelSpec) -> _abi.AmpParams:
     ap.contact_body_mask = mask
     ap.num_bodies = len(names)
     return ap
+
+
+# ---- AnymalTerrain (anymal_terrain.py)
+# as Anymal: no fused-kernel task id, no shipped table, z = baseInitState.pos[2], the (32, 32, 48, 48, 192) instance
+TASK_INFO["AnymalTerrain"] = (None, None, _abi.MG_ANYMAL_TERRAIN_OBS, _abi.MG_ANYMAL_DOFS, 0.62, 48)
+RENDER_DEFAULTS["AnymalTerrain"] = dict(RENDER_DEFAULTS["Anymal"])
+ANYMAL_TERRAIN_HIP_DOFS = (0, 3, 6, 9)   # anymal_terrain.py:359
+# the learn.* key of each column of rew_scale / episode_sums (_abi.ANYMAL_TERRAIN_REWARDS; anymal_terrain.py:63-76)
+ANYMAL_TERRAIN_REWARD_KEYS = (
+    "linearVelocityXYRewardScale", "linearVelocityZRewardScale", "angularVelocityZRewardScale",
+    "angularVelocityXYRewardScale", "orientationRewardScale", "torqueRewardScale", "jointAccRewardScale",
+    "baseHeightRewardScale", "feetAirTimeRewardScale", "kneeCollisionRewardScale", "feetStumbleRewardScale",
+    "actionRateRewardScale", "hipRewardScale")
+
+
+def anymal_terrain_spec(spec: M.ModelSpec, cfg: dict) -> M.ModelSpec:
+    """The quadruped as the task configures it, on a copy (anymal_terrain.py:218-231): DOF_MODE_EFFORT, so no drive
+    gain and no joint spring; the joint damping and the effort limits stay the asset's; no link angular damping."""
+    import copy
+    spec = copy.deepcopy(spec)
+    if spec.num_dofs != _abi.MG_ANYMAL_DOFS or spec.fixed_base:
+        raise ValueError("AnymalTerrain needs a free-base 12-DOF model")
+    for n in spec.nodes[1:]:
+        n.stiffness = 0.0
+        n.drive_kp = 0.0
+    spec.angular_damping = 0.0
+    return spec
+
+
+def anymal_terrain_height_points():
+    """init_height_points (anymal_terrain.py:503-513): the (140, 2) grid of the 1 m x 1.6 m rectangle without its
+    centre lines, x major, each coordinate the fp32 product 0.1 * k as torch forms it"""
+    y = np.float32(0.1) * np.array([-5, -4, -3, -2, -1, 1, 2, 3, 4, 5], np.float32)
+    x = np.float32(0.1) * np.array([-8, -7, -6, -5, -4, -3, -2, 2, 3, 4, 5, 6, 7, 8], np.float32)
+    gx, gy = np.meshgrid(x, y, indexing="ij")
+    return np.stack([gx.ravel(), gy.ravel()], axis=1).astype(np.float32)
+
+
+def anymal_terrain_noise_scale_vec(cfg: dict):
+    """_get_noise_scale_vec (anymal_terrain.py:174-186): each entry a product of Python floats, rounded to fp32 once"""
+    learn = cfg["env"]["learn"]
+    level = learn["noiseLevel"]
+    v = np.zeros(_abi.MG_ANYMAL_TERRAIN_OBS, np.float32)
+    v[0:3] = learn["linearVelocityNoise"] * level * learn["linearVelocityScale"]
+    v[3:6] = learn["angularVelocityNoise"] * level * learn["angularVelocityScale"]
+    v[6:9] = learn["gravityNoise"] * level
+    v[12:24] = learn["dofPositionNoise"] * level * learn["dofPositionScale"]
+    v[24:36] = learn["dofVelocityNoise"] * level * learn["dofVelocityScale"]
+    v[36:176] = learn["heightMeasurementNoise"] * level * learn["heightMeasurementScale"]
+    return v
+
+
+def anymal_terrain_params(cfg: dict, spec: M.ModelSpec) -> _abi.AnymalTerrainParams:
+    """AnymalTerrain constants (anymal_terrain.py:53-105, 174-186, 245-292), computed where the reference computes them:
+    products and differences of Python floats in double, rounded to fp32 once.  The terrain fields (env_length,
+    env_rows, env_cols, custom_origins, hf_*) are the task's to fill once it has built its Terrain."""
+    env = cfg["env"]
+    learn, ctl, ter = env["learn"], env["control"], env["terrain"]
+    ap = _abi.AnymalTerrainParams()
+    ap.lin_vel_scale, ap.ang_vel_scale = float(learn["linearVelocityScale"]), float(learn["angularVelocityScale"])
+    ap.dof_pos_scale, ap.dof_vel_scale = float(learn["dofPositionScale"]), float(learn["dofVelocityScale"])
+    ap.height_meas_scale = float(learn["heightMeasurementScale"])
+    dt = ctl["decimation"] * cfg["sim"]["dt"]   # anymal_terrain.py:95: Python floats
+    for k, key in enumerate(ANYMAL_TERRAIN_REWARD_KEYS):
+        ap.rew_scale[k] = learn[key] * dt
+    ap.rew_termination = learn["terminalReward"] * dt
+    # what feet_air_time advances by is self.dt as VecTask.__init__ leaves it (vec_task.py:242 overwrites the task's
+    # decimation * dt with sim_params.dt, a C float): the reference's quirk, kept
+    ap.dt = float(np.float32(cfg["sim"]["dt"]))
+    ap.Kp, ap.Kd, ap.action_scale, ap.torque_clip = float(ctl["stiffness"]), float(ctl["damping"]), \
+        float(ctl["actionScale"]), 80.0
+    angles = env["defaultJointAngles"]
+    for j, name in enumerate(spec.dof_names):
+        ap.default_dof_pos[j] = float(angles[name])
+    b = env["baseInitState"]
+    state = list(b["pos"]) + list(b["rot"]) + list(b["vLinear"]) + list(b["vAngular"])
+    if len(state) != 13:
+        raise ValueError("baseInitState must hold pos 3, rot 4, vLinear 3, vAngular 3")
+    for c, x in enumerate(state):
+        ap.base_init_state[c] = float(x)
+    rng = env["randomCommandVelocityRanges"]
+    for c, key in enumerate(("linear_x", "linear_y", "yaw")):   # the yaw range is the heading's (anymal_terrain.py:411)
+        lo, hi = float(rng[key][0]), float(rng[key][1])
+        ap.command_lo[c], ap.command_span[c] = lo, hi - lo
+    urdf = env.get("urdfAsset", {}) or {}
+    foot_name, knee_name = urdf.get("footName", ANYMAL_FOOT), urdf.get("kneeName", ANYMAL_KNEE)
+    names = [x.name for x in spec.bodies]
+    knees = [i for i, s in enumerate(names) if knee_name in s]
+    feet = [i for i, s in enumerate(names) if foot_name in s]
+    if len(knees) != 4 or len(feet) != 4 or ANYMAL_BASE not in names:
+        raise ValueError(f"AnymalTerrain needs a body named 'base', four {knee_name} and four {foot_name} bodies")
+    ap.base_body = names.index(ANYMAL_BASE)
+    for k in range(4):
+        ap.knee_body[k], ap.foot_body[k], ap.hip_dof[k] = knees[k], feet[k], ANYMAL_TERRAIN_HIP_DOFS[k]
+    ap.num_bodies = len(names)
+    ap.allow_knee_contacts = int(bool(learn["allowKneeContacts"]))
+    ap.add_noise = int(bool(learn["addNoise"]))
+    for c, x in enumerate(anymal_terrain_noise_scale_vec(cfg)):
+        ap.noise_scale_vec[c] = float(x)
+    ap.max_episode_length_s = float(learn["episodeLength_s"])
+    ap.max_episode_length = int(learn["episodeLength_s"] / dt + 0.5)
+    ap.curriculum = int(bool(ter["curriculum"]))
+    ap.env_length, ap.env_rows, ap.env_cols, ap.custom_origins = 0.0, 1, 1, 0
+    for k, x in enumerate(anymal_terrain_height_points().ravel()):
+        ap.height_points[k] = float(x)
+    ap.clip_actions = float(env.get("clipActions", math.inf))
+    ap.clip_obs = float(env.get("clipObservations", math.inf))
+    return ap

@@ -4,6 +4,7 @@ from .cartpole import Cartpole
 from .shadow_hand import ShadowHand
 from .franka_reach_ma import FrankaReachMA
 from .anymal import Anymal
+from .anymal_terrain import AnymalTerrain
 from .humanoid_amp import HumanoidAMP
 from .quadcopter import Quadcopter
 
@@ -15,6 +16,7 @@ isaacgym_task_map = {
     "ShadowHand": ShadowHand,
     "FrankaReachMA": FrankaReachMA,
     "Anymal": Anymal,
+    "AnymalTerrain": AnymalTerrain,
     "HumanoidAMP": HumanoidAMP,
     "Quadcopter": Quadcopter,
 }

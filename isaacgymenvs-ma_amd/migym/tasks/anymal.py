@@ -31,8 +31,9 @@ from .base.simulate_task import SimulateTask, state_tensors
 _TASKS_DIR = os.path.dirname(os.path.abspath(__file__))
 
 
-def _load_model(env) -> M.ModelSpec:
-    """the robot's model table from env.asset: a JSON table (modelTable) or a URDF (assetRoot + assetFileName)"""
+def _load_model(env, task="Anymal", builder="anymal_c") -> M.ModelSpec:
+    """the robot's model table from env.asset: a JSON table (modelTable) or a URDF (assetRoot + assetFileName);
+    ``task`` and ``builder`` (the tools/build_models.py command that writes one) name themselves in the error"""
     asset = env.get("asset", {}) or {}
     tried = []
     table = asset.get("modelTable")
@@ -50,9 +51,9 @@ def _load_model(env) -> M.ModelSpec:
             return M.load_urdf(path, "anymal_c", fix_base=bool(urdf.get("fixBaseLink", False)),
                                collapse_fixed=True, replace_cylinder_with_capsule=True, effort_limits=True)
     raise FileNotFoundError(
-        "Anymal: no ANYmal model found (tried " + (", ".join(tried) or "nothing: env.asset is empty") +
+        f"{task}: no ANYmal model found (tried " + (", ".join(tried) or "nothing: env.asset is empty") +
         ").  No ANYmal asset ships with this package: set env.asset.modelTable to a JSON model table -- "
-        "`python tools/build_models.py anymal_c` writes one from the reference's URDF -- or "
+        f"`python tools/build_models.py {builder}` writes one from the reference's URDF -- or "
         "env.asset.assetRoot / assetFileName to the URDF")
 
 

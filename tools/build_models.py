@@ -34,6 +34,9 @@ them from migym/assets/*.json.
             tests/golden/anymal_c.json and not shipped under migym/assets: 13 bodies (base, then
             {LF,RF,LH,RH}_{HIP,THIGH,SHANK}), 12 DOFs, 37 primitive geoms, the URDF's inertials (52.13 kg) and its
             effort limits (80 N m); the task sets the drive gains (env.control).
+  AnymalTerrain  assets/urdf/anymal_c/urdf/anymal_minimal.urdf, the same options (anymal_terrain.py:218-231), written
+            only on request (`build_models.py anymal_minimal [OUT.json]`): the same 13 bodies and 12 DOFs with 9
+            primitive geoms; the task puts the DOFs in effort mode.  The tests run the task on the Anymal fixture.
   HumanoidAMP  assets/mjcf/amp_humanoid.xml (amp/humanoid_amp_base.py:176-226: angular_damping 0.01,
             max_angular_velocity 100, self-collision filter 0).  A TEST FIXTURE, written to
             tests/golden/amp_humanoid.json and not shipped under migym/assets: 15 bodies, 28 DOFs, 18 geoms, 122 self
@@ -187,6 +190,18 @@ def anymal_c():
     return spec
 
 
+ANYMAL_MINIMAL_URDF = "assets/urdf/anymal_c/urdf/anymal_minimal.urdf"
+
+
+def anymal_minimal():
+    """ANYmal C as the reference's AnymalTerrain task loads it (anymal_terrain.py:218-231, cfg urdfAsset.file): the
+    minimal URDF with the same options as anymal_c(); the task puts the DOFs in effort mode itself"""
+    spec = M.load_urdf(os.path.join(REF, ANYMAL_MINIMAL_URDF), "anymal_c", fix_base=False, collapse_fixed=True,
+                       replace_cylinder_with_capsule=True, effort_limits=True)
+    spec.angular_damping = 0.0      # anymal_terrain.py:225
+    return spec
+
+
 AMP_MJCF = "assets/mjcf/amp_humanoid.xml"
 AMP_JSON = os.path.join(HERE, "..", "tests", "golden", "amp_humanoid.json")
 
@@ -291,6 +306,11 @@ if __name__ == "__main__":
         # the Anymal table alone (Anymal's env.asset.modelTable): `build_models.py anymal_c [OUT.json]`
         path = sys.argv[2] if len(sys.argv) > 2 else ANYMAL_JSON
         anymal_c().to_json(path)
+        print("wrote", path)
+    elif sys.argv[1:2] == ["anymal_minimal"]:
+        # AnymalTerrain's table (env.asset.modelTable): `build_models.py anymal_minimal [OUT.json]`
+        path = sys.argv[2] if len(sys.argv) > 2 else "anymal_minimal.json"
+        anymal_minimal().to_json(path)
         print("wrote", path)
     elif sys.argv[1:2] == ["amp_humanoid"]:
         # the AMP humanoid's table alone (HumanoidAMP's env.asset.modelTable): `build_models.py amp_humanoid [OUT.json]`
