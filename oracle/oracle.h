@@ -19,6 +19,12 @@
  *     kernels use — with the same contact set, PGS row order and integrator,
  *     and is pinned by analytic known-answer tests (free fall, energy,
  *     pendulum, joint limits, resting contact) in tests/test_oracle_physics.py.
+ *   heightfield ground (orc_set_heightfield): the facet rule of DESIGN.md §15 in place of the plane z = 0 for
+ *     every ground candidate, in fp64 (and in `real` in the fp32 twin); everything after the contact list -- the
+ *     tangent basis, the Jacobian rows, the row order, PGS / TGS -- is the code the flat step runs.  Pinned on the
+ *     CPU before it judges a kernel (tests/test_heightfield_oracle_host.py): bit-equal on a zero field, contact
+ *     for contact against the definition in numpy, against its own flat step in a rotated frame on planes, and
+ *     by analytic answers on one facet (rest, sliding, both tangent-basis branches) and in a V-shaped valley.
  */
 #ifndef MIGYM_ORACLE_H
 #define MIGYM_ORACLE_H
@@ -35,6 +41,16 @@ float orc_uniform(uint64_t seed, uint64_t env, uint64_t counter, uint32_t k);
  * row; `threads` OpenMP threads (0 = library default). */
 int orc_simulate(const mg_model* m, const mg_sim_params* p, int32_t n, float* root_states, float* dof_state,
                  const float* dof_actuation, float* sensors, float* dof_force, int32_t threads);
+
+/* The ground of every later call in this library: hf == NULL (the default) the plane z = 0; otherwise the heightfield
+ * of DESIGN.md §15, read in every substep by orc_simulate, orc_simulate_views, orc_contacts, orc_contacts_full,
+ * orc_contacts_marks, orc_contacts_phases and orc_step_flips.  hf->heights and hf->env_origins are HOST pointers,
+ * kept and not copied; hf->hmax is used by orc_step_flips alone (the oracle culls nothing).  The env_origins row of an
+ * actor is env_base + its index inside the call: env e of orc_simulate_views / orc_step_flips reads row env_base + e,
+ * the one-actor hooks (orc_contacts*) read row env_base -- a caller that steps actor e through a one-row view passes
+ * env_base = e.  The descriptor is process-wide and read-only during a call: set it between calls, never from inside
+ * an OpenMP region.  Returns 0, or -1 on a NULL table, nx or ny < 2, dx <= 0 or a negative env_base (the plane then). */
+int orc_set_heightfield(const mg_heightfield* hf, int32_t env_base);
 
 /* gym.simulate on the full state views: object/goal root rows, PD targets and rigid-body states
  * of hand tasks included (views->dof_targets may be NULL = zero targets). */
@@ -71,9 +87,20 @@ int orc_box_box_edge(const double* shape, const double* hb, double off, double* 
 int orc_hull_distance(const mg_model* m, const double* pl, int32_t n, double* out);
 int orc_hull_core_contact(const mg_model* m, const double* shape, double rB, double off, double* out);
 /* parity-test support: bit mask of the physics discontinuities env e's gym.simulate passes near (delta m / rad
- * of a contact / pair / limit threshold with the row in use; drives within df of saturation; seg_box_sat ties) */
+ * of a contact / pair / limit threshold with the row in use; drives within df of saturation; seg_box_sat ties).
+ * On a heightfield, from the fp64 run at every substep: 256 a ground candidate within 1e-5 cells of a cell edge or
+ * diagonal with another plane behind it, 512 one whose geom the kernels' cull drops (c.z - (hmax - oz) - bound >= off)
+ * -- both when the row is used or its gap within delta of the threshold, 256 also when only the other side touches --
+ * and 1024 a candidate on another facet than at the substep before with its gap within delta of the threshold on
+ * either of the two */
 int orc_step_flips(const mg_model* m, const mg_sim_params* p, const mg_state_views* v, int32_t e, double delta,
                    double df);
+/* test support: the contacts of env e's gym.simulate, substep by substep, without writing the views: records of 13
+ * doubles (substep, nodeA, geomA, nodeB, p(3), n(3), d, the largest normal impulse the solve gave the row -- 0 for a
+ * row it never used --, the tangential speed of the contact point at the substep's start); returns the count, or -1
+ * on a model with a free object or with env_props bound */
+int orc_step_rows(const mg_model* m, const mg_sim_params* p, const mg_state_views* v, int32_t e, double* out,
+                  int32_t cap);
 /* world poses of the gym rigid bodies (n_bodies x 13, velocity at body COM) */
 int orc_rigid_body_states(const mg_model* m, const float* root13, const float* dof2, float* out);
 

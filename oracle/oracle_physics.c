@@ -86,6 +86,22 @@ static __thread int orc_cap_hit = 0;
 /* the hull narrowphase's decision thresholds, scaled by orc_step_flips' variants (1 = the build's) */
 static __thread struct { double fe, ang, cop; int seam, face; double marg; } orc_hv = {1.0, 1.0, 1.0, 0, -1, 0.0};
 
+/* The heightfield of orc_set_heightfield: host pointers, kept and not copied, read-only during a call.
+ * orc_hf_env is the env_origins row of the actor a thread is working on. */
+static struct { int on, nx, ny, base; const float* tab; const float* org; float dx, x0, y0, hmax; } orc_hf;
+static __thread int orc_hf_env = 0;
+static __thread int orc_hf_next = 0;       /* contact.hf of the contact being pushed */
+/* the geom whose ground candidates collide() is emitting: centre height and the radius the kernel's cull uses */
+static __thread double orc_hf_cz = 0.0, orc_hf_bound = 0.0;
+/* orc_step_flips on a field: thresholds are out by `delta`; `hit` collects bits 256 (a candidate next to a crease that
+ * is in contact on one side only) and 1024; facet[] is each candidate's facet (2 (i ny + j) + upper) at the previous
+ * substep, in emission order */
+#define ORC_HF_EDGE_EPS 1e-5 /* of a cell (heightfield_ref.EDGE_EPS) */
+#define ORC_HF_MAXCAND 1024
+#ifndef ORC_FP32
+static __thread struct { int on, k, n_prev, hit; double delta; int facet[ORC_HF_MAXCAND]; } orc_hft;
+#endif
+
 typedef real v3[3];
 
 /* ---------------------------------------------------------------- small math */
@@ -208,6 +224,7 @@ typedef struct {
   int amb;   /* made by a geom-object candidate set with a decision in its ambiguity band (bit 16) */
   int edge;  /* box_box_edge's contact (orc_contacts_marks bit 16: what a state set reaches) */
   int phase; /* the part of collide() that emitted it (ORC_PH_*; orc_contacts_phases) */
+  int hf;    /* on a heightfield: 1 next to a crease with another plane behind it, 2 the kernel's hmax cull drops the geom */
 } contact;
 
 static int nv_of(const mg_model* m) { return (m->fixed_base ? 0 : 6) + m->num_dofs; }
@@ -495,13 +512,111 @@ static int push_contact(contact* out, int n, int cap, int nodeA, int gA, int nod
   c->amb = 0;
   c->edge = orc_edge_next;
   c->phase = orc_phase;
+  c->hf = orc_hf_next;
+  orc_hf_next = 0;
   orc_ill_next = 0;
   orc_edge_next = 0;
   return n + 1;
 }
 
-/* sphere (center c, radius r) vs ground plane z = 0 */
+/* the cell and the cell coordinates of the world point (X, Y) clamped to the grid rectangle */
+static void hf_locate(real X, real Y, int* i, int* j, real* fu, real* fv) {
+  const real dx = orc_hf.dx, x0 = orc_hf.x0, y0 = orc_hf.y0;
+  const real x1 = x0 + (orc_hf.nx - 1) * dx, y1 = y0 + (orc_hf.ny - 1) * dx;
+  X = X < x0 ? x0 : (X > x1 ? x1 : X);
+  Y = Y < y0 ? y0 : (Y > y1 ? y1 : Y);
+  const real u = (X - x0) / dx, v = (Y - y0) / dx;
+  int ii = (int)floor(u), jj = (int)floor(v);
+  ii = ii < 0 ? 0 : (ii > orc_hf.nx - 2 ? orc_hf.nx - 2 : ii);
+  jj = jj < 0 ? 0 : (jj > orc_hf.ny - 2 ? orc_hf.ny - 2 : jj);
+  *i = ii; *j = jj; *fu = u - ii; *fv = v - jj;
+}
+/* triangle (lower: fu >= fv) of cell (i, j) as a plane: its height at cell coordinates (fu, fv) and its unit normal */
+static void hf_plane(int i, int j, int lower, real fu, real fv, real* h, real* n) {
+  const float* c = orc_hf.tab + (size_t)i * orc_hf.ny + j;
+  const real h00 = c[0], h01 = c[1], h10 = c[orc_hf.ny], h11 = c[orc_hf.ny + 1], dx = orc_hf.dx;
+  real gx, gy;
+  if (lower) {
+    *h = h00 + (h10 - h00) * fu + (h11 - h10) * fv;
+    gx = (h10 - h00) / dx; gy = (h11 - h10) / dx;
+  } else {
+    *h = h00 + (h11 - h01) * fu + (h01 - h00) * fv;
+    gx = (h11 - h01) / dx; gy = (h01 - h00) / dx;
+  }
+  const real l = sqrt(gx * gx + gy * gy + (real)1.0);
+  n[0] = -gx / l; n[1] = -gy / l; n[2] = (real)1.0 / l;
+}
+
+/* a ground candidate (centre c, radius r) on the field: the facet under it, gap (z - h) n.z - r, point c - r n */
+static int sphere_field(contact* out, int n, int cap, int node, int g, const real* c, real r, real off) {
+  const real ox = orc_hf.org ? orc_hf.org[3 * (size_t)orc_hf_env] : 0.0f;
+  const real oy = orc_hf.org ? orc_hf.org[3 * (size_t)orc_hf_env + 1] : 0.0f;
+  const real oz = orc_hf.org ? orc_hf.org[3 * (size_t)orc_hf_env + 2] : 0.0f;
+  const real X = c[0] + ox, Y = c[1] + oy;
+  int i, j;
+  real fu, fv, h, nf[3];
+  hf_locate(X, Y, &i, &j, &fu, &fv);
+  const int lower = fu >= fv;
+  hf_plane(i, j, lower, fu, fv, &h, nf);
+  const real d = (c[2] - (h - oz)) * nf[2] - r;
+  int mark = 0;
+#ifndef ORC_FP32
+  if (orc_hft.on) {
+    const double delta = orc_hft.delta, thr = off - delta; /* off is the widened threshold here */
+    /* next to a crease (the diagonal, or a cell edge with a cell behind it) whose other side is another plane */
+    real near = fabs(fu - fv);
+    if (i > 0 && fu < near) near = fu;
+    if (j > 0 && fv < near) near = fv;
+    if (i < orc_hf.nx - 2 && 1.0 - fu < near) near = 1.0 - fu;
+    if (j < orc_hf.ny - 2 && 1.0 - fv < near) near = 1.0 - fv;
+    if (near < ORC_HF_EDGE_EPS) {
+      static const int nud[6][2] = {{2, 0}, {-2, 0}, {0, 2}, {0, -2}, {2, -2}, {-2, 2}};
+      int differs = 0, touch_any = d < off;
+      for (int q = 0; q < 6; q++) {
+        int i2, j2;
+        real fu2, fv2, h2, n2[3];
+        hf_locate(X + nud[q][0] * ORC_HF_EDGE_EPS * orc_hf.dx, Y + nud[q][1] * ORC_HF_EDGE_EPS * orc_hf.dx, &i2, &j2,
+                  &fu2, &fv2);
+        const int low2 = fu2 >= fv2;
+        if (i2 == i && j2 == j && low2 == lower) continue;
+        hf_plane(i2, j2, low2, fu + (i - i2), fv + (j - j2), &h2, n2); /* that plane, extended to this point */
+        const real d2 = (c[2] - (h2 - oz)) * n2[2] - r;
+        if (fabs(n2[0] - nf[0]) + fabs(n2[1] - nf[1]) + fabs(n2[2] - nf[2]) > 1e-9 || fabs(d2 - d) > 1e-9) differs = 1;
+        if (d2 < off) touch_any = 1;
+      }
+      if (differs) {
+        mark |= 1;
+        if (touch_any && !(d < off) && orc_hft.on == 1) orc_hft.hit |= 256; /* in contact on the other side only: no row to ask */
+      }
+    }
+    /* the kernel's cull of the whole geom against the field's highest point */
+    if (orc_hf_cz - ((double)orc_hf.hmax - oz) - orc_hf_bound >= thr && d < off) mark |= 2;
+    /* the facet of this candidate at the previous substep (the pass of orc_step_flips that follows them) */
+    const int fid = 2 * (i * orc_hf.ny + j) + !lower, kk = orc_hft.on == 1 ? orc_hft.k++ : ORC_HF_MAXCAND;
+    if (kk < ORC_HF_MAXCAND) {
+      if (kk < orc_hft.n_prev && orc_hft.facet[kk] != fid) {
+        const int fp = orc_hft.facet[kk], ip = (fp / 2) / orc_hf.ny, jp = (fp / 2) % orc_hf.ny;
+        real hp, np_[3];
+        hf_plane(ip, jp, !(fp & 1), fu + (i - ip), fv + (j - jp), &hp, np_);
+        const real dp = (c[2] - (hp - oz)) * np_[2] - r;
+        if (fabs(d - thr) < delta || fabs(dp - thr) < delta) orc_hft.hit |= 1024;
+      }
+      orc_hft.facet[kk] = fid;
+    }
+  }
+#endif
+  if (d < off) {
+    real p[3] = {c[0] - r * nf[0], c[1] - r * nf[1], c[2] - r * nf[2]};
+    orc_hf_next = mark;
+    n = push_contact(out, n, cap, node, g, -1, -1, p, nf, d);
+    orc_hf_next = 0;
+  }
+  return n;
+}
+
+/* sphere (center c, radius r) vs the ground: the plane z = 0, or the field of orc_set_heightfield */
 static int sphere_plane(contact* out, int n, int cap, int node, int g, const real* c, real r, real off) {
+  if (orc_hf.on) return sphere_field(out, n, cap, node, g, c, r, off);
   real d = c[2] - r;
   if (d < off) {
     real p[3] = {c[0], c[1], c[2] - r}, nz[3] = {0, 0, 1};
@@ -2259,6 +2374,12 @@ static int collide(const mg_model* m, const mg_sim_params* p, const kin* k, cont
     int nd = m->geom_node[g], ty = m->geom_type[g];
     real c[3], R[3][3];
     geom_world(m, k, g, c, R);
+    if (orc_hf.on) { /* what the kernel's cull of this geom sees (orc_step_flips bit 512) */
+      const double s0 = m->geom_size[g][0], s1 = m->geom_size[g][1], s2 = m->geom_size[g][2];
+      orc_hf_cz = c[2];
+      orc_hf_bound = ty == MG_GT_SPHERE ? s0 : ty == MG_GT_CAPSULE ? s0 + s1 : sqrt(s0 * s0 + s1 * s1 + s2 * s2);
+      if (ty == MG_GT_BOX) orc_hf_bound = fabs(R[2][0]) * s0 + fabs(R[2][1]) * s1 + fabs(R[2][2]) * s2; /* its lowest corner */
+    }
     if (ty == MG_GT_SPHERE) {
       n = sphere_plane(out, n, cap, nd, g, c, m->geom_size[g][0], off);
     } else if (ty == MG_GT_CAPSULE) {
@@ -2286,6 +2407,7 @@ static int collide(const mg_model* m, const mg_sim_params* p, const kin* k, cont
     }
   }
   orc_phase = ORC_PH_OBJ_GROUND;
+  orc_hf_bound = 1e30; /* (the kernels take no free object on a field: nothing to cull) */
   if (m->obj_type == MG_GT_BOX) {
     for (int corner = 0; corner < 8; corner++) {
       real l[3] = {(corner & 1 ? 1 : -1) * m->obj_size[0], (corner & 2 ? 1 : -1) * m->obj_size[1],
@@ -2940,6 +3062,17 @@ static void simulate_env(const mg_model* m0, const mg_sim_params* p, float* root
   free(mdr);
 }
 
+int orc_set_heightfield(const mg_heightfield* hf, int32_t env_base) {
+  memset(&orc_hf, 0, sizeof(orc_hf));
+  if (!hf) return 0;
+  if (!hf->heights || hf->nx < 2 || hf->ny < 2 || !(hf->dx > 0.0f) || env_base < 0) return -1;
+  orc_hf.tab = hf->heights; orc_hf.org = hf->env_origins;
+  orc_hf.nx = hf->nx; orc_hf.ny = hf->ny; orc_hf.base = env_base;
+  orc_hf.dx = hf->dx; orc_hf.x0 = hf->x0; orc_hf.y0 = hf->y0; orc_hf.hmax = hf->hmax;
+  orc_hf.on = 1;
+  return 0;
+}
+
 int orc_simulate_views(const mg_model* m, const mg_sim_params* p, int32_t n, const mg_state_views* v,
                        int32_t threads) {
   int nd = m->num_dofs, ns = m->num_sensors;
@@ -2949,6 +3082,7 @@ int orc_simulate_views(const mg_model* m, const mg_sim_params* p, int32_t n, con
 #pragma omp parallel for schedule(dynamic, 16)
 #endif
   for (int e = 0; e < n; e++) {
+    orc_hf_env = orc_hf.base + e;
     simulate_env(m, p, v->root_states + (size_t)13 * rows * e, v->dof_state + (size_t)2 * nd * e,
                  v->dof_actuation ? v->dof_actuation + (size_t)nd * e : 0,
                  v->dof_targets ? v->dof_targets + (size_t)nd * e : 0, v->sensors ? v->sensors + (size_t)6 * ns * e : 0,
@@ -2986,6 +3120,7 @@ int orc_contacts_full(const mg_model* m, const mg_sim_params* p, const float* ro
   if (m->obj_type) load_object(&s, root13 + 13);
   forward_kinematics(m, &s, &k);
   contact con[MAXC];
+  orc_hf_env = orc_hf.base;
   int nc = collide(m, p, &k, con, cap < MAXC ? cap : MAXC);
   for (int i = 0; i < nc; i++) {
     real* o = out + 11 * i;
@@ -3022,6 +3157,7 @@ static int contacts_marks(const mg_model* m, const mg_sim_params* p, const float
   orc_pair_offset = delta;
   orc_tie_delta = delta;
   orc_amb_hit = 0;
+  orc_hf_env = orc_hf.base;
   int nc = collide(m, &pw, &k, con, cap < MAXC ? cap : MAXC);
   orc_pair_offset = 0.0;
   orc_tie_delta = -1.0;
@@ -3114,6 +3250,10 @@ int orc_step_flips(const mg_model* m0, const mg_sim_params* p, const mg_state_vi
   pw.contact_offset = (float)(p->contact_offset + delta);
   pw.limit_margin = (float)(p->limit_margin + delta);
   int flags = 0;
+  orc_hf_env = orc_hf.base + e;
+  orc_hft.n_prev = 0;
+  orc_hft.hit = 0;
+  orc_hft.delta = delta;
   for (int st = 0; st < p->substeps; st++) {
     /* drives near saturation at this substep's state */
     for (int i = 1; i < m->num_nodes; i++) {
@@ -3135,7 +3275,18 @@ int orc_step_flips(const mg_model* m0, const mg_sim_params* p, const mg_state_vi
       orc_pair_offset = delta;
       orc_tie_delta = delta;
       orc_amb_lost_at = -1;
+      /* on a field this pass also follows every ground candidate's facet from substep to substep (bit 1024) and
+       * finds the candidates next to a crease that touch on its other side only (bit 256) */
+      orc_hft.on = orc_hf.on;
+      orc_hft.k = 0;
       const int na = collide(m, &pw, &kc, all, MAXC);
+      orc_hft.on = 0;
+      orc_hft.n_prev = orc_hft.k < ORC_HF_MAXCAND ? orc_hft.k : ORC_HF_MAXCAND;
+      /* a row next to a crease, or one the kernel's cull drops: when it is within delta of the threshold (whether
+       * used or not is then undecided too) -- the rows in use are asked after the solve below */
+      for (int i = 0; i < na; i++)
+        if (all[i].hf && all[i].nodeB == -1 && fabs(all[i].d - p->contact_offset) < delta)
+          flags |= (all[i].hf & 1 ? 256 : 0) | (all[i].hf & 2 ? 512 : 0);
       const int lost = orc_amb_lost_at;
       orc_amb_lost_at = -1;
       if (na + (lost >= 0) > cap)
@@ -3152,7 +3303,9 @@ int orc_step_flips(const mg_model* m0, const mg_sim_params* p, const mg_state_vi
     orc_tie_hit = 0;
     orc_amb_hit = 0;
     orc_cap_hit = 0;
+    orc_hft.on = orc_hf.on ? 2 : 0; /* marks only: the facets were followed above */
     substep(m, &pw, &sw, tau, so);
+    orc_hft.on = 0;
     orc_pair_offset = 0.0;
     orc_tie_delta = -1.0;
     if (orc_tie_hit) flags |= 8;
@@ -3166,6 +3319,8 @@ int orc_step_flips(const mg_model* m0, const mg_sim_params* p, const mg_state_vi
       if (fabs(ct->d - thr) < delta && so->lmax[3 * c] > eps) flags |= 1;
       if (ct->ill && so->lmax[3 * c] > eps) flags |= 32;
       if (ct->amb && so->lmax[3 * c] > eps) flags |= 16;
+      if ((ct->hf & 1) && so->lmax[3 * c] > eps) flags |= 256;
+      if ((ct->hf & 2) && so->lmax[3 * c] > eps) flags |= 512;
     }
     for (int r = 3 * so->ncon; r < so->nrows; r++) {
       const int i = so->row_ref[r];
@@ -3174,10 +3329,58 @@ int orc_step_flips(const mg_model* m0, const mg_sim_params* p, const mg_state_vi
     }
     substep(m, p, &s, tau, so);
   }
+  flags |= orc_hft.hit;
+  orc_hft.hit = 0;
   free(so);
   free(mdr);
   return flags;
 }
+
+#ifndef ORC_FP32
+/* test support: the contacts of env e's gym.simulate substep by substep (the state views are read, not written):
+ * records of 13 doubles (substep, nodeA, geomA, nodeB, p(3), n(3), d, the largest normal impulse the solve gave the
+ * row: 0 for a row it never used, the tangential speed of the contact point at the substep's start).  Returns the
+ * count (at most cap). */
+int orc_step_rows(const mg_model* m, const mg_sim_params* p, const mg_state_views* v, int32_t e, double* out,
+                  int32_t cap) {
+  if (m->obj_type || v->env_props) return -1;
+  const int nd = m->num_dofs;
+  const float* act = v->dof_actuation ? v->dof_actuation + (size_t)nd * e : 0;
+  astate s;
+  memset(&s, 0, sizeof(s));
+  load_state(m, v->root_states + (size_t)13 * e, v->dof_state + (size_t)2 * nd * e, &s);
+  s.tgt = v->dof_targets ? v->dof_targets + (size_t)nd * e : 0;
+  real tau[MAXN];
+  for (int i = 0; i < nd; i++) tau[i] = act ? act[i] : 0.0;
+  substep_out* so = (substep_out*)calloc(1, sizeof(substep_out));
+  orc_hf_env = orc_hf.base + e;
+  int n = 0;
+  for (int st = 0; st < p->substeps; st++) {
+    static __thread kin k0;
+    real nu[MAXV], J[MAXV];
+    forward_kinematics(m, &s, &k0);
+    for (int c = 0; c < 6 && !m->fixed_base; c++) nu[c] = s.nu0[c];
+    for (int i = 1; i < m->num_nodes; i++) nu[dof_col(m, i)] = s.qd[i];
+    substep(m, p, &s, tau, so);
+    for (int c = 0; c < so->ncon && n < cap; c++, n++) {
+      const contact* ct = &so->con[c];
+      double* o = out + 13 * n;
+      real t[2][3], vt[2] = {0, 0};
+      tangent_basis(ct->n, t[0], t[1]);
+      for (int q = 0; q < 2; q++) {
+        jac_row(m, &k0, ct->nodeA, ct->nodeB, ct->p, t[q], J);
+        for (int a = 0; a < nv_of(m); a++) vt[q] += J[a] * nu[a];
+      }
+      o[12] = sqrt(vt[0] * vt[0] + vt[1] * vt[1]);
+      o[0] = st; o[1] = ct->nodeA; o[2] = ct->geomA; o[3] = ct->nodeB;
+      for (int a = 0; a < 3; a++) { o[4 + a] = ct->p[a]; o[7 + a] = ct->n[a]; }
+      o[10] = ct->d; o[11] = so->lmax[3 * c];
+    }
+  }
+  free(so);
+  return n;
+}
+#endif
 
 int orc_mass_matrix(const mg_model* m, const mg_sim_params* p, const float* root13, const float* dof2,
                     real* M_out) {
@@ -3218,6 +3421,7 @@ int orc_contacts(const mg_model* m, const mg_sim_params* p, const float* root13,
   forward_kinematics(m, &s, &k);
   contact con[MAXC];
   int c = cap < MAXC ? cap : MAXC;
+  orc_hf_env = orc_hf.base;
   int nc = collide(m, p, &k, con, c);
   for (int i = 0; i < nc; i++) {
     real* o = out + 9 * i;

@@ -70,6 +70,8 @@ def lib():
         l.orc_hull_core_contact.argtypes = [P, P, C.c_double, C.c_double, P]
         l.orc_step_flips.argtypes = [P, C.POINTER(_abi.SimParams), C.POINTER(_abi.StateViews), C.c_int32, C.c_double,
                                      C.c_double]
+        l.orc_set_heightfield.argtypes = [C.POINTER(_abi.Heightfield), C.c_int32]
+        l.orc_step_rows.argtypes = [P, C.POINTER(_abi.SimParams), C.POINTER(_abi.StateViews), C.c_int32, P, C.c_int32]
         l.orc_dr_apply.argtypes = [C.POINTER(_abi.DrApplyArgs)]
         l.orc_dr_noise.argtypes = [C.POINTER(_abi.DrNoiseArgs)]
         _lib = l
@@ -91,12 +93,49 @@ def lib_f32():
         l.orc_simulate_views.argtypes = [P, C.POINTER(_abi.SimParams), C.c_int32, C.POINTER(_abi.StateViews),
                                          C.c_int32]
         l.orc_contacts_full.argtypes = [P, C.POINTER(_abi.SimParams), P, P, P, C.c_int32]   # rows of 11 floats
+        l.orc_set_heightfield.argtypes = [C.POINTER(_abi.Heightfield), C.c_int32]
         _lib32 = l
     return _lib32
 
 
 def f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+_field = None     # the arrays the libraries point into
+
+
+def set_heightfield(fld, env_base=0):
+    """orc_set_heightfield on the fp64 checker and on its fp32 twin: fld has H (nx, ny) fp32, nx, ny, dx, x0, y0, hmax
+    and origins ((n, 3) fp32 or None), as tests/heightfield_ref.Field; None puts the plane back.  The origin row of an
+    actor is env_base + its index inside the call (oracle.h)."""
+    global _field
+    if fld is None:
+        for l in (lib(), lib_f32()):
+            l.orc_set_heightfield(None, 0)
+        _field = None
+        return
+    H = f32(fld.H)
+    org = None if fld.origins is None else f32(fld.origins)
+    hf = _abi.Heightfield(heights=H.ctypes.data, nx=fld.nx, ny=fld.ny, dx=fld.dx, x0=fld.x0, y0=fld.y0, hmax=fld.hmax,
+                          env_origins=p(org))
+    for l in (lib(), lib_f32()):
+        assert l.orc_set_heightfield(C.byref(hf), int(env_base)) == 0
+    _field = (H, org)
+
+
+class heightfield:
+    """with heightfield(fld, env_base): the oracle's ground is the field inside the block, the plane after it"""
+
+    def __init__(self, fld, env_base=0):
+        self.fld, self.base = fld, env_base
+
+    def __enter__(self):
+        set_heightfield(self.fld, self.base)
+        return self
+
+    def __exit__(self, *exc):
+        set_heightfield(None)
 
 
 def i64(a):
@@ -211,6 +250,16 @@ def step_flips(model_np, sp, host, delta=1e-4, df=1e-2):
     v = host.views()
     return np.array([lib().orc_step_flips(model_np.ctypes.data, C.byref(sp), C.byref(v), e, delta, df)
                      for e in range(host.n)], np.int32)
+
+
+def step_rows(model_np, sp, host, e, cap=512):
+    """orc_step_rows of env e of a host (views() as for step_flips): rows (substep, nodeA, geomA, nodeB, p(3), n(3), d,
+    largest normal impulse, tangential speed of the contact point at the substep's start)"""
+    v = host.views()
+    out = np.zeros(13 * cap)
+    n = lib().orc_step_rows(model_np.ctypes.data, C.byref(sp), C.byref(v), e, p(out), cap)
+    assert n >= 0
+    return out[: 13 * n].reshape(n, 13)
 
 
 def rigid_body_states(model_np, root13, dof2, nbodies):

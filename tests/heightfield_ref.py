@@ -13,6 +13,9 @@ state sets shared by tests/test_heightfield_host.py (the reference alone, on the
     collide()'s emission order: sphere centre, capsule ends, box corners), with contacts_ref's marks for the threshold
     band and for candidates next to a cell edge or diagonal; contacts between geoms come from the oracle's own list.
   * scan(): mg_height_scan's rule.
+  * rough_case(), chain_case(), terrain_case(): states stepped on a field that is no plane -- the rough field, the
+    task's stairs, a generated AnymalTerrain terrain -- against the oracle on the same field (pyoracle.set_heightfield;
+    pinned on the CPU by tests/test_heightfield_oracle_host.py), admitted by the oracle alone.
 """
 import copy
 
@@ -164,6 +167,37 @@ def plane_setup(model):
     return spec, mnp, sp
 
 
+def nudged(host, rng):
+    """the host with every position moved by +-SENS_EPS (an fp32 step's rounding; one draw of the signs), in place"""
+    host.root[:, 0:3] += TP.SENS_EPS * rng.choice([-1.0, 1.0], (host.n, 3))
+    host.dof[..., 0] += TP.SENS_EPS * rng.choice([-1.0, 1.0], host.dof[..., 0].shape)
+    return host
+
+
+def insensitive(nud, ref):
+    """per state: the oracle's step from the nudged state stays within a quarter of the one-step tolerances of its step
+    from the state itself (tree_physics_ref.states' criterion)"""
+    return ~(PS.env_bad(nud.dof[..., 0], ref.dof[..., 0], 0.25 * 2e-4, 0) |
+             PS.env_bad(nud.dof[..., 1], ref.dof[..., 1], 0.25 * 2e-3, 0.25 * 2e-3) |
+             PS.env_bad(nud.root[:, 0:7], ref.root[:, 0:7], 0.25 * 2e-4, 0) |
+             PS.env_bad(nud.root[:, 7:13], ref.root[:, 7:13], 0.25 * 2e-3, 0.25 * 2e-3))
+
+
+def admit_on_field(spec, mnp, sp, fld, root, dof, act, tgt, rng):
+    """(the fp64 oracle's Host after one step on the field, admitted per state, why, candidates, flags): the one
+    admission rule of the stepped-field cases, the oracle's alone -- contact candidates within capacity before and
+    after the step, no orc_step_flips flag (the field's bits 256 / 512 / 1024 included), finite, and insensitive()"""
+    mk = lambda: LF.Host(spec, root, dof, act, tgt)    # noqa: E731
+    ref = field_step(fld, mk(), mnp, sp)
+    cand = np.maximum(field_candidates(fld, mnp, sp, root, dof), field_candidates(fld, mnp, sp, ref.root, ref.dof))
+    flags = field_flags(fld, mk(), mnp, sp)
+    ok = (cand <= sp.max_contacts) & (flags == 0) & np.isfinite(ref.root).all(1)
+    why = {"capacity": int((cand > sp.max_contacts).sum()), "flags": int((flags != 0).sum())}
+    ok &= insensitive(field_step(fld, nudged(mk(), rng), mnp, sp), ref)
+    why["all"] = int((~ok).sum())
+    return ref, ok, why, cand, flags
+
+
 def slope_case(model, tgs, substeps=2, kind="slope"):
     """The admitted states of (model, solver) on planes, as LF.case.  kind "slope": one plane for the case, random tilt
     and direction, sampled by a 33 x 33 field; kind "facets": actor e on triangle e % 8 of facet_field(), its root over
@@ -198,14 +232,8 @@ def slope_case(model, tgs, substeps=2, kind="slope"):
     pre = LF.Host(spec, root, dof, act, tgt)
     ok = (np.maximum(before, after) <= sp.max_contacts) & (pre.flags_each(mnp, sps) == 0) & np.isfinite(ref.root).all(1)
     r2 = np.random.default_rng([43, SLOPE_MODELS.index(model)])
-    nud = LF.Host(spec, root, dof, act, tgt)
-    nud.root[:, 0:3] += TP.SENS_EPS * r2.choice([-1.0, 1.0], (nn, 3))
-    nud.dof[..., 0] += TP.SENS_EPS * r2.choice([-1.0, 1.0], (nn, spec.num_dofs))
-    nud.simulate_each(mnp, sps)
-    ok &= ~(PS.env_bad(nud.dof[..., 0], ref.dof[..., 0], 0.25 * 2e-4, 0) |
-            PS.env_bad(nud.dof[..., 1], ref.dof[..., 1], 0.25 * 2e-3, 0.25 * 2e-3) |
-            PS.env_bad(nud.root[:, 0:7], ref.root[:, 0:7], 0.25 * 2e-4, 0) |
-            PS.env_bad(nud.root[:, 7:13], ref.root[:, 7:13], 0.25 * 2e-3, 0.25 * 2e-3))
+    nud = nudged(LF.Host(spec, root, dof, act, tgt), r2).simulate_each(mnp, sps)
+    ok &= insensitive(nud, ref)
     want = max(LF.BATCHES[model])
     idx = np.flatnonzero(ok)[:want]
     assert len(idx) == want, f"{model}: the pool admits only {len(idx)} of the {want} states"
@@ -307,15 +335,39 @@ def candidates(spec, root13, q):
     return out
 
 
-def ground_list(spec, sp, fld, env, root13, q, delta=CR.DELTA):
+def oracle_candidates(spec, mnp, sp, root13, dof2, zmax):
+    """(cands, rest): candidates() with the points of the oracle's own kinematics (the packed model's fp32 tables;
+    candidates() runs on the spec, a few 1e-8 m away).  The oracle's plane list -- no field set -- at contact offset
+    zmax gives every candidate whose lowest point e.z - r is below zmax, in emission order, as p = e - r z (its list
+    ends at 64 entries, fewer than the tree's box corners, hence the height); rest: candidates()'s other entries"""
+    big = copy.copy(sp)
+    big.contact_offset = zmax
+    rows = O.contacts_full(mnp, big, root13, dof2, 64)
+    rows = rows[rows[:, 2] == -1]
+    assert len(rows) < 64        # (the pair contacts that follow may be cut: they are not read here)
+    ref = candidates(spec, root13, dof2[:, 0])
+    out, k = [], 0
+    for row in rows:
+        g = spec.geoms[int(row[1])]
+        r = float(F(g.size[0])) if g.gtype in (M.GT_SPHERE, M.GT_CAPSULE) else 0.0
+        e = row[4:7] + np.array([0.0, 0.0, r])
+        while not (ref[k][0] == int(row[1]) and np.abs(ref[k][2] - e).max() < 1e-6):     # the same candidate: in order
+            k += 1
+        out.append((ref[k][0], ref[k][1], e, r, ref[k][4], ref[k][5], k))
+        k += 1
+    used = {c[6] for c in out}
+    return [c[:6] for c in out], [c for i, c in enumerate(ref) if i not in used]
+
+
+def ground_list(spec, sp, fld, env, root13, q, delta=CR.DELTA, cands=None):
     """(rows, marks) of one actor's ground contacts on the field by DESIGN.md §15, thresholds moved out by delta as
     orc_contacts_marks does: BAND_IN / BAND_OUT for a gap within delta of contact_offset; AMB for a candidate within
     EDGE_EPS cells of a cell edge or the diagonal whose other facet puts the gap on the other side of the threshold (or
     which is inside the band on either facet), ILL where it lies that close to a crease at all (its normal and point
-    may be either facet's)"""
+    may be either facet's).  cands: the candidates, where they are not candidates()'s (oracle_candidates())"""
     off, o = float(sp.contact_offset), fld.origin(env)
     rows, marks = [], []
-    for gi, node, e, r, bound, c in candidates(spec, root13, q):
+    for gi, node, e, r, bound, c in (candidates(spec, root13, q) if cands is None else cands):
         X, Y = e[0] + o[0], e[1] + o[1]
         h, n, (i, j, fu, fv) = facet(fld, X, Y)
         d = (e[2] - (h - o[2])) * n[2] - r
@@ -434,3 +486,310 @@ def scan_roots(rng, n, fld):
 
 def scan_origins(rng, n):
     return np.concatenate([rng.uniform(-0.5, 0.5, (n, 2)), rng.uniform(-0.2, 0.2, (n, 1))], 1).astype(F)
+
+
+# ------------------------------------------------------------------------------------------------ rough ground, stepped
+ROUGH_MODELS = ("T16-free", "Anymal", "AMP")
+# The T16-free tree is smaller than a tread of the stairs (0.3 m): dropped anywhere, most of its states stand on one
+# level, and pressed in until half of them use two facets more than 5 % of the pool exceed its 24 contacts on the
+# risers.  place_straddling() puts it where it straddles a riser instead.
+STAIRS_MODELS = ("T16-free", "Anymal")
+STEEP = 0.57735             # tangent_basis_t's branch: |n.x| at or above it takes the y axis
+# place()'s quantile of the feet's lifts (0: every foot pressed in or touching), and how far (m) the state is lowered
+# after that.  Chosen so that the cases meet test_heightfield_host's conditions on the oracle alone
+PRESS = {("T16-free", "rough"): 0.25, ("T16-free", "stairs"): 0.0, ("Anymal", "rough"): 0.0, ("Anymal", "stairs"): 0.0, ("AMP", "rough"): 0.5}
+SINK = {("T16-free", "rough"): 0.03, ("T16-free", "stairs"): 0.0, ("Anymal", "rough"): 0.0, ("Anymal", "stairs"): 0.0, ("AMP", "rough"): 0.0}
+SLIP = 1e-2                 # m/s: a contact point this fast along its facet has friction rows that matter
+
+
+def stairs_field(origins=None):
+    """migym.terrain.pyramid_stairs_terrain at AnymalTerrain's scales (horizontal 0.1 m, vertical 0.005 m, steps of
+    0.15 m every 0.31 m: three cells of tread, and between two treads one cell that climbs 0.15 m, gradient 1.5), on a
+    65 x 65 grid centred on the origin"""
+    from migym import terrain as TR
+    t = TR.pyramid_stairs_terrain(TR.SubTerrain(width=65, length=65, vertical_scale=0.005, horizontal_scale=0.1), 0.31, 0.15)
+    return Field(t.height_field_raw.astype(np.float64) * 0.005, 0.1, -3.2, -3.2, origins)
+
+
+def step_field(kind, origins=None):
+    return rough_field(origins=origins) if kind == "rough" else stairs_field(origins)
+
+
+def on_field(fld, fn, n):
+    """[fn(e) for e < n] with the oracle's ground set to the field and actor e's origin row bound (env_base = e: the
+    calls below hand the oracle one-row views, whose env index is 0)"""
+    try:
+        out = []
+        for e in range(n):
+            if e == 0 or fld.origins is not None:
+                O.set_heightfield(fld, e if fld.origins is not None else 0)
+            out.append(fn(e))
+        return out
+    finally:
+        O.set_heightfield(None)
+
+
+def field_step(fld, host, mnp, sp, fp32=False):
+    """one simulate of every actor of an LF.Host on the field (the oracle, or its fp32 twin), in place"""
+    import ctypes as C
+    lib = O.lib_f32() if fp32 else O.lib()
+
+    def one(e):
+        v = host.views(e, e + 1)
+        lib.orc_simulate_views(mnp.ctypes.data, C.byref(sp), 1, C.byref(v), 1)
+    on_field(fld, one, host.n)
+    return host
+
+
+def field_flags(fld, host, mnp, sp):
+    import ctypes as C
+
+    def one(e):
+        v = host.views(e, e + 1)
+        return O.lib().orc_step_flips(mnp.ctypes.data, C.byref(sp), C.byref(v), 0, PS.STEP_DELTA, PS.STEP_DF)
+    return np.array(on_field(fld, one, host.n), np.int32)
+
+
+def field_candidates(fld, mnp, sp, root, dof):
+    return np.array(on_field(fld, lambda e: len(O.contacts(mnp, sp, root[e], dof[e], 96)), len(root)))
+
+
+class _One:
+    """one actor of a host, as the hooks that take a host and an env index want it"""
+
+    def __init__(self, host, e):
+        self.v = host.views(e, e + 1)
+
+    def views(self):
+        return self.v
+
+
+def field_rows(fld, host, mnp, sp):
+    """per actor O.step_rows on the field"""
+    return on_field(fld, lambda e: O.step_rows(mnp, sp, _One(host, e), 0), host.n)
+
+
+def place_one(spec, fld, e, row, q, xy, q_lift, sink, off=None):
+    """actor e's root row put at world xy over the field (place()'s rule); with off, also the planes (normal and
+    offset, rounded) of the ground candidates that then touch by the definition (gap below off)"""
+    row = np.array(row, F)
+    o = fld.origin(e)
+    row[0:2] = xy - o[0:2]
+    cs = candidates(spec, row, q)
+    gaps = np.array([c[2][2] - c[3] for c in cs])
+    low = gaps.min()
+    at = [facet(fld, c[2][0] + o[0], c[2][1] + o[1])[:2] for c in cs]
+    lift = [(low + c[3]) / nrm[2] + (h - o[2]) - c[2][2] for c, g, (h, nrm) in zip(cs, gaps, at) if g < low + 0.05]
+    dz = np.quantile(lift, q_lift) - sink
+    row[2] += dz
+    if off is None:
+        return row, None
+    dz = float(row[2]) - (float(row[2]) - dz)       # (what the fp32 row took)
+    touch = [tuple(np.round(np.append(nrm, nrm[2] * float(h - o[2])), 6)) for c, (h, nrm) in zip(cs, at)
+             if (c[2][2] + dz - (h - o[2])) * nrm[2] - c[3] < off]
+    return row, touch
+
+
+def place(spec, fld, root, dof, rng, span, q=0.5, sink=0.0, xy=None):
+    """pool states put over the field: random xy within +-span of the grid's centre (world coordinates; the origin, if
+    any, is taken out), and raised so that the share q of the ground candidates that touch the plane in the pool state
+    have at most the gap over their facets that the lowest of them has over the plane (the others hang above theirs):
+    feet near the ground under them, some pressed in and some free"""
+    root = np.array(root, F)
+    n = len(root)
+    xy = rng.uniform(-span, span, (n, 2)) if xy is None else xy
+    for e in range(n):
+        root[e] = place_one(spec, fld, e, root[e], dof[e, :, 0], xy[e], q, sink)[0]
+    return root
+
+
+STRADDLE_TRIES, STRADDLE_MOST, STRADDLE_STEEP = 64, 14, 3
+
+
+def place_straddling(spec, fld, root, dof, rng, span, q, sink, off):
+    """place() for a body smaller than a tread of the stairs: per actor the first of STRADDLE_TRIES random xy at which,
+    by the definition alone (no step is run), the candidates that touch lie on two or more planes, STRADDLE_STEEP or
+    more of them on a facet steep along x or y, and are at most STRADDLE_MOST (room under the contact capacity for the
+    step to add some)"""
+    root = np.array(root, F)
+    for e in range(len(root)):
+        for xy in rng.uniform(-span, span, (STRADDLE_TRIES, 2)):
+            row, touch = place_one(spec, fld, e, root[e], dof[e, :, 0], xy, q, sink, off)
+            if len(set(touch)) >= 2 and len(touch) <= STRADDLE_MOST and \
+                    sum(max(abs(t[0]), abs(t[1])) >= STEEP for t in touch) >= STRADDLE_STEEP:
+                break
+        root[e] = row
+    return root
+
+
+def rough_case(model, tgs, kind="rough", origins=False, substeps=2):
+    """The admitted states of (model, solver) on a field that is no plane, as slope_case: kind "rough" (rough_field())
+    or "stairs" (stairs_field()); origins: per-actor env origins (random xy, oz +-0.2).  T16-free keeps its
+    self-collision pairs.  Admission is the oracle's alone: candidates within capacity before and after the step, no
+    orc_step_flips flag (the field's bits 256 / 512 / 1024 included), not sensitive to the SENS_EPS nudge, finite.
+    Keys: spec, mnp, sp, fld, idx, scanned, root / dof / act / tgt, ref (the fp64 oracle's Host after the step), level
+    (the same over the plane at the height under each root), rows (O.step_rows per state), cand."""
+    key = ("rough case", kind, model, tgs, origins, substeps)
+    if key in _cache:
+        return _cache[key]
+    spec, mnp, sp0 = LF.setup(model)
+    root, dof, act, tgt, _ = LF.pool(model)
+    nn = len(root)
+    rng = np.random.default_rng([53, ROUGH_MODELS.index(model), int(kind == "stairs"), int(origins)])
+    org = np.concatenate([rng.uniform(-0.5, 0.5, (nn, 2)), rng.uniform(-0.2, 0.2, (nn, 1))], 1) if origins else None
+    fld = step_field(kind, org)
+    root = np.array(root, F)
+    if model == "T16-free":
+        root[:, 2] -= 0.5     # back down: linkforce_ref raised the tree off the ground
+    half = 0.5 * (fld.nx - 1) * fld.dx
+    if (model, kind) == ("T16-free", "stairs"):
+        root = place_straddling(spec, fld, root, dof, rng, 0.8 * half, PRESS[model, kind], SINK[model, kind],
+                                float(sp0.contact_offset))
+    else:
+        root = place(spec, fld, root, dof, rng, 0.8 * half, PRESS[model, kind], SINK[model, kind])
+    sp = LF.sp_at(sp0, None, substeps, tgs)
+    ref, ok, why, cand, flags = admit_on_field(spec, mnp, sp, fld, root, dof, act, tgt,
+                                               np.random.default_rng([59, ROUGH_MODELS.index(model)]))
+    want = max(LF.BATCHES[model])
+    idx = np.flatnonzero(ok)[:want]
+    assert len(idx) == want, f"{model} {kind}: the pool admits only {len(idx)} of the {want} states ({why})"
+    pick = lambda x: None if x is None else np.ascontiguousarray(x[idx])    # noqa: E731
+    out = dict(spec=spec, mnp=mnp, sp=sp, idx=idx, scanned=int(idx[-1]) + 1, root=pick(root), dof=pick(dof), act=pick(act),
+               tgt=pick(tgt), cand=int(cand[idx].max()), flags=flags, why=why)
+    out["fld"] = Field(fld.H, fld.dx, fld.x0, fld.y0, None if org is None else org[idx])
+    h = LF.Host(spec, out["root"], out["dof"], out["act"], out["tgt"])
+    for name in ("root", "dof", "sensors", "dof_force", "ncf"):
+        getattr(h, name)[:] = getattr(ref, name)[idx]
+    out["ref"] = h
+    # the plane at the height under each root: the oracle's flat step of the state lowered by that height
+    hz = np.array([float(facet(out["fld"], *(out["root"][k, 0:2] + out["fld"].origin(k)[0:2]))[0]) - out["fld"].origin(k)[2]
+                   for k in range(want)])
+    low = np.array(out["root"])
+    low[:, 2] -= hz.astype(F)
+    lev = LF.Host(spec, low, out["dof"], out["act"], out["tgt"]).simulate_each(mnp, [sp] * want)
+    lev.root[:, 2] += hz.astype(F)
+    out["level"] = lev
+    out["rows"] = field_rows(out["fld"], LF.Host(spec, out["root"], out["dof"], out["act"], out["tgt"]), mnp, sp)
+    _cache[key] = out
+    return out
+
+
+def row_stats(c):
+    """(multi, steep_x, steep_y) per admitted state of a rough_case: ground rows the solve uses (a normal impulse above
+    1e-9 at some visit) lie on two or more facets in one substep; one of them has |n.x| >= STEEP / |n.y| >= STEEP and a
+    contact point moving along its facet faster than SLIP"""
+    multi, sx, sy = [], [], []
+    for rows in c["rows"]:
+        used = rows[(rows[:, 3] == -1) & (rows[:, 11] > 1e-9)]
+        # a facet is its plane: the normal and the offset n . (p - d n) (two treads of the stairs share a normal only)
+        plane = lambda r: tuple(np.round(np.append(r[7:10], r[7:10] @ r[4:7] - r[10]), 6))    # noqa: E731
+        multi.append(any(len({plane(r) for r in used[used[:, 0] == st]}) >= 2 for st in np.unique(used[:, 0])))
+        fast = used[used[:, 12] > SLIP]
+        sx.append(bool((np.abs(fast[:, 7]) >= STEEP).any()))
+        sy.append(bool((np.abs(fast[:, 8]) >= STEEP).any()))
+    return np.array(multi), np.array(sx), np.array(sy)
+
+
+def chain_case(model, tgs, launches=4, fp32=True):
+    """rough_case(model, tgs)'s states stepped `launches` times by the oracle's fp32 twin (in the kernel's place: launch k
+    starts from launch k - 1's output), the fp64 oracle restarted from the same state each time.  Per launch: (input
+    Host, ref Host, admitted (bool per state): the admission of rough_case on that launch's inputs)."""
+    key = ("chain", model, tgs, launches, fp32)
+    if key in _cache:
+        return _cache[key]
+    c = rough_case(model, tgs)
+    out, cur = [], LF.Host(c["spec"], c["root"], c["dof"], c["act"], c["tgt"])
+    for _ in range(launches):
+        inp, ref, ok = chain_admit(c, cur.root, cur.dof)
+        out.append((inp, ref, ok))
+        cur = field_step(c["fld"], LF.Host(c["spec"], cur.root, cur.dof, c["act"], c["tgt"]), c["mnp"], c["sp"], fp32=fp32)
+    _cache[key] = out
+    return out
+
+
+def chain_admit(c, root, dof):
+    """(input Host, the fp64 oracle's Host after one step from it, admitted per state) on rough_case c's field"""
+    ref, ok, _, _, _ = admit_on_field(c["spec"], c["mnp"], c["sp"], c["fld"], root, dof, c["act"], c["tgt"],
+                                      np.random.default_rng(67))
+    return LF.Host(c["spec"], root, dof, c["act"], c["tgt"]), ref, ok
+
+
+def take(h, keep):
+    """the rows `keep` of a step's outputs (a Host or a namespace), as a namespace"""
+    import types
+    return types.SimpleNamespace(**{k: np.asarray(getattr(h, k))[keep] for k in ("root", "dof", "sensors", "dof_force", "ncf")})
+
+
+# ------------------------------------------------------------------------------------------------ AnymalTerrain's physics
+TERRAIN_COLS = (0, 2, 3)     # of the generated terrain's five columns: pyramid slope, stairs, discrete obstacles
+
+
+def terrain_case(origins):
+    """AnymalTerrain's effort-mode model at the task's sim parameters on a terrain generated by migym.terrain.Terrain (2
+    levels x 5 columns of 8 m maps, seeded, curriculum: a slope, two stairs columns, obstacles, stepping stones), the
+    standing states of anymal_ref on the harder level's slope, stairs and obstacle maps, off the central platform.
+    origins: per-actor env origins, each map's own origin (the task itself runs in world coordinates).  Keys: spec, mnp,
+    sp, p (the restatement's params), fld, root, dof, actions, n."""
+    key = ("terrain case", origins)
+    if key in _cache:
+        return _cache[key]
+    import anymal_ref as AR
+    import anymal_terrain_ref as R
+    from migym import terrain as TR
+    _, _, _, root, dof, _, _ = AR.physics_states("standing")
+    n = len(root)
+    spec, mnp, sp, ap = R.task_model(R.task_cfg(n))
+    state = np.random.get_state()
+    np.random.seed(7)       # the terrain's draws
+    t = TR.Terrain(dict(terrainType="trimesh", mapLength=8.0, mapWidth=8.0, numLevels=2, numTerrains=5, curriculum=True,
+                        terrainProportions=[0.1, 0.1, 0.35, 0.25, 0.2]), n)
+    np.random.set_state(state)
+    table = (t.height_field_raw.astype(F) * F(t.vertical_scale)).astype(F)
+    rng = np.random.default_rng(73)
+    col = np.array(TERRAIN_COLS)[np.arange(n) % len(TERRAIN_COLS)]
+    off = rng.uniform(1.7, 3.5, (n, 2)) * rng.choice([-1.0, 1.0], (n, 2))       # off the 3 m platform, inside the 8 m map
+    org = t.env_origins[1, col].astype(F)
+    xy = org[:, 0:2].astype(np.float64) + off
+    fld = Field(table, t.horizontal_scale, -t.border_size, -t.border_size, org if origins else None)
+    root = place(spec, fld, np.array(root, F), dof, rng, 0.0, 0.0, 0.0, xy)
+    actions = np.random.default_rng(41).uniform(-1, 1, (n, 12)).astype(F)
+    out = dict(spec=spec, mnp=mnp, sp=sp, p=R.params_from(ap), fld=fld, root=root, dof=np.array(dof, F), actions=actions, n=n,
+               col=col)
+    _cache[key] = out
+    return out
+
+
+TERRAIN_CHECKS = (("root pose", "root", slice(0, 7), 2e-4, 0), ("dof pos", "dof", 0, 2e-4, 0),
+                  ("root twist", "root", slice(7, 13), 2e-3, 2e-3), ("dof vel", "dof", 1, 2e-3, 2e-3))
+
+
+def terrain_compare(test, c, got, root, dof, eff):
+    """one launch's outputs (root, dof, ncf) against the fp64 oracle stepped on the field from (root, dof) with the
+    efforts eff, by test_one_decimation_step_matches_the_oracle's rule: the one-step tolerances, net contact forces to
+    1 % of the batch's largest, a disagreeing env only where orc_step_flips flags its step, the flags reaching at most
+    5 % of the envs.  Returns (the oracle's Host, flags, worst err / tolerance per check)."""
+    n = len(root)
+    mk = lambda: LF.Host(c["spec"], root, dof, eff)    # noqa: E731
+    ref = field_step(c["fld"], mk(), c["mnp"], c["sp"])
+    flags = field_flags(c["fld"], mk(), c["mnp"], c["sp"])
+    for x in (got.root, got.dof, got.ncf):
+        assert np.isfinite(x).all(), f"{test}: not finite"
+    assert np.abs(got.dof[..., 0] - dof[..., 0]).max() > 1e-4, "the step moved nothing"
+    pick = lambda h, name, sl: (h.root[:, sl] if name == "root" else h.dof[..., sl])    # noqa: E731
+    checks = [(nm, pick(got, a, sl), pick(ref, a, sl), atol, rtol) for nm, a, sl, atol, rtol in TERRAIN_CHECKS]
+    root_ref = quat_close(np.asarray(got.root, np.float64), ref.root)
+    checks[0] = ("root pose", got.root[:, 0:7], root_ref[:, 0:7], 2e-4, 0)
+    checks.append(("net contact forces", got.ncf, ref.ncf, 1e-2 * max(1.0, float(np.abs(ref.ncf).max())), 0))
+    bad, worst = np.zeros(n, bool), {}
+    for name, a, b, atol, rtol in checks:
+        a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+        eb = PS.env_bad(a, b, atol, rtol)
+        ratio = (np.abs(a - b) / (atol + rtol * np.abs(b))).reshape(n, -1).max(1)
+        worst[name] = float(ratio[flags == 0].max())
+        print(f"{test} {name}: max err {np.abs(a - b).max():.3g} (atol {atol:.3g}), err / tolerance on unflagged envs "
+              f"{worst[name]:.3g}, envs outside {int(eb.sum())} / {n}")
+        PS.record(test, name, a, b, envs_outside=int(eb.sum()), atol=atol, rtol=rtol)
+        bad |= eb
+    print(f"{test}: {int((flags != 0).sum())} of {n} envs flagged")
+    PS.assert_steps_explained(test, bad[None], flags[None], sens=None, reach_cap=PS.REACH_CAP, allow_unexplained=0.0)
+    return ref, flags, worst

@@ -394,6 +394,46 @@ def test_one_decimation_step_matches_the_oracle(lib, n):
     PS.assert_steps_explained(test, bad[None], flags[None], sens=None, reach_cap=PS.REACH_CAP, allow_unexplained=0.0)
 
 
+@pytest.mark.parametrize("origins", [False, True], ids=["world", "origins"])
+def test_decimation_step_matches_the_oracle_on_generated_terrain(lib, origins):
+    """The same on the ground the task is for: a terrain generated by migym.terrain.Terrain (heightfield_ref.terrain_case:
+    the standing states on its slope, stairs and obstacle maps), in world coordinates as the task runs and once with
+    each map's origin as the actors' env origins.  Four launches of (mg_anymal_terrain_pre, mg_sim_simulate), teacher-
+    forced: after each the fp64 oracle is stepped on the same field from the state the launch started from with the
+    kernel's own efforts, and compared by the rule above (heightfield_ref.terrain_compare; the CPU suite runs it with
+    the oracle's fp32 twin in the kernel's place).  Measured (MI355X), worst err / tolerance over the four launches, world
+    and origins: root pose 0.014, dof pos 0.18, root twist 0.19, dof vel 0.22 (first launch, the pressed feet pushed
+    out; 0.045 by the fourth), net contact forces 0.050; no env flagged, none outside."""
+    import heightfield_ref as HF
+    c = HF.terrain_case(origins)
+    n, fld = c["n"], c["fld"]
+    s = TerrainSim(lib, n, cfg=R.task_cfg(n, **{"terrain.terrainType": "plane"}))
+    tab = dev(fld.H)
+    org = dev(fld.origins) if origins else None
+    hf = _abi.Heightfield(heights=tab.data_ptr(), nx=fld.nx, ny=fld.ny, dx=fld.dx, x0=fld.x0, y0=fld.y0, hmax=fld.hmax,
+                          env_origins=_abi.ptr(org))
+    _abi.check(lib.mg_sim_set_heightfield(s.sim, C.byref(hf)), lib)
+    try:
+        s.root.copy_(dev(c["root"]))
+        s.dof.copy_(dev(c["dof"].reshape(n * 12, 2)))
+        s.actions.copy_(dev(c["actions"]))
+        for k in range(4):
+            root, dof = s.root.cpu().numpy(), s.dof.view(n, 12, 2).cpu().numpy()
+            s.ncf.fill_(float("nan"))   # every row must be written
+            s.pre()
+            s.simulate()
+            torch.cuda.synchronize()
+            eff = s.act.view(n, 12).cpu().numpy()
+            assert np.array_equal(eff, R.pre_step(c["p"], c["actions"], dof)[1]), "the kernel's efforts are the restatement's"
+            got = types.SimpleNamespace(root=s.root.cpu().numpy(), dof=s.dof.view(n, 12, 2).cpu().numpy(),
+                                        ncf=s.ncf.view(n, s.nb, 3).cpu().numpy())
+            test = f"test_decimation_step_on_generated_terrain[{'origins' if origins else 'world'}-launch {k}]"
+            _, _, worst = HF.terrain_compare(test, c, got, root, dof, eff)
+            PS._REPORT.setdefault(test, {})["err_over_tol"] = worst
+    finally:
+        s.close()
+
+
 # ------------------------------------------------------------------------------------------------ the task
 def terrain_cfg(N, **env):
     """a generated 2 x 3 curriculum terrain, short episodes, the fixture model"""

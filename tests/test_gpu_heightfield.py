@@ -14,6 +14,10 @@ linkforce_ref.outside) and contacts_ref's BOUNDS["none"]; nothing here is wider.
   7. the refusals, and the fused tasks' NotImplementedError.
   8. the height scan, bit for bit outside the rounding band.
   9. through make(): zero and level fields on Anymal.
+ 10. one launch (2 substeps, PGS and TGS, with and without env origins) on rough ground and on the task's stairs against
+     the fp64 oracle stepped on the same field (orc_set_heightfield): contacts of one actor on several facets, facets
+     that change between the substeps, and on the stairs tangent_basis_t's second branch (|n.x| >= 0.57735).
+ 11. four launches chained on the rough field, the oracle restarted from the kernel's own state at each.
 """
 import ctypes as C
 import types
@@ -234,6 +238,55 @@ def test_rough_ground_past_capacity(lib):
         got = sim.contacts(fld, root, dof, 64)
     assert max(len(g) for g in got) == cap
     CR.compare("test_rough_ground_past_capacity", got, lists, "none", max_contacts=cap)
+
+
+# ------------------------------------------------------------------------------------------------ 10. / 11. stepped fields
+STEPPED = [(m, tgs, n, "rough", org) for m in HF.ROUGH_MODELS for tgs in (False, True) for n in LF.BATCHES[m]
+           for org in (False, True)] + \
+    [(m, tgs, n, "stairs", org) for m in HF.STAIRS_MODELS for tgs in (False, True) for n in LF.BATCHES[m]
+     for org in (False, True)]
+
+
+def first(fld, n):
+    return HF.Field(fld.H, fld.dx, fld.x0, fld.y0, None if fld.origins is None else fld.origins[:n])
+
+
+@pytest.mark.parametrize("model,tgs,n,kind,origins", STEPPED)
+def test_stepped_field_matches_the_oracle_on_the_field(lib, model, tgs, n, kind, origins):
+    """Measured (MI355X): see DESIGN.md §15"""
+    c = HF.rough_case(model, tgs, kind, origins)
+    spec, mnp = c["spec"], c["mnp"]
+    assert c["sp"].substeps == 2
+    with Sim(lib, spec, mnp, c["sp"], n) as sim:
+        assert sim.lanes() == LF.LANES[model]
+        got = sim.run(first(c["fld"], n), c["root"], c["dof"], c["act"], c["tgt"])
+    assert np.abs(got.dof[..., 0] - c["dof"][:n, :, 0]).max() > 1e-4, "the step moved nothing"
+    name = f"[{model}-{sides(tgs)}-{n}-{kind}-{'origins' if origins else 'world'}]"
+    worst = HF.compare_step("test_stepped_field" + name, spec, got, c["ref"], n)
+    PS._REPORT.setdefault("heightfield stepped" + name, {})["err_over_tol"] = worst
+
+
+@pytest.mark.parametrize("model,tgs", [(m, tgs) for m in ("T16-free", "Anymal") for tgs in (False, True)])
+def test_chained_launches_match_the_oracle_at_every_launch(lib, model, tgs):
+    """launch k starts from the kernel's output of launch k - 1; the oracle is restarted from that state, which it
+    admits by rough_case's conditions (at most 5 % per launch are not).  The oracle's work between the launches is four
+    one-actor passes over 67 states per launch; the whole test takes under 0.1 s"""
+    c = HF.rough_case(model, tgs)
+    spec, mnp, fld = c["spec"], c["mnp"], c["fld"]
+    n = len(c["idx"])
+    root, dof = c["root"], c["dof"]
+    with Sim(lib, spec, mnp, c["sp"], n) as sim:
+        for k in range(4):
+            got = sim.run(fld, root, dof, c["act"], c["tgt"])
+            _, ref, ok = HF.chain_admit(c, root, dof)
+            print(f"launch {k}: {int((~ok).sum())} of {n} states not admitted")
+            assert (~ok).sum() <= LF.DISCARD_CAP * n
+            keep = np.flatnonzero(ok)
+            name = f"test_chained_launches[{model}-{sides(tgs)}-launch {k}]"
+            worst = HF.compare_step(name, spec, HF.take(got, keep), HF.take(ref, keep), len(keep))
+            PS._REPORT.setdefault("heightfield " + name, {})["err_over_tol"] = worst
+            assert np.isfinite(got.root).all() and np.isfinite(got.dof).all()
+            root, dof = got.root, got.dof
 
 
 # ------------------------------------------------------------------------------------------------ 7. refusals

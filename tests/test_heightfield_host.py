@@ -8,6 +8,10 @@ of them, the frame argument holds, and the inputs of tests/test_gpu_heightfield.
   * slope_case(): at most DISCARD_CAP of the drawn states are passed over by the oracle-decided conditions; the slope
     moves the oracle's own result out of the one-step tolerances (against its flat step under unrotated gravity) in at
     least 90 % of the kept states; the oracle's fp32 twin passes the rule the GPU test applies.
+  * rough_case(), chain_case(), terrain_case(): the states stepped on rough ground, on the task's stairs and on a generated
+    terrain meet their conditions on the oracle alone -- at most 5 % passed over, used rows on two or more facets in
+    at least half of the states, steep rows along x and along y on the stairs in at least a tenth, the field moves the
+    oracle's result in at least 90 % -- and the oracle's fp32 twin passes the rule the GPU tests apply.
   * the rough-ground contact sets and the scan points: at most 5 % of a set's contacts are ambiguous and at most 5 % of
     its envs can need an exemption; at most 2 % of the scan points sit in the rounding band.
   * the C ABI: the new symbols are exported, mg_heightfield_sizeof() is the ctypes mirror's, mg_version() is 7, and
@@ -184,6 +188,94 @@ def test_rough_ground_sets_are_admitted(model, n):
         # (the oracle's kinematics run on the packed model's fp32 tables, this reference's on the spec: a few 1e-8 m,
         # far below contacts_ref's bounds of 5e-6)
         np.testing.assert_allclose(r[keep][:, 4:], ro[keepo][:, 4:], atol=2e-7, rtol=0)
+
+
+# ------------------------------------------------------------------------------------------------ admission: stepped
+ROUGH = [(m, tgs, "rough", org) for m in HF.ROUGH_MODELS for tgs in (False, True) for org in (False, True)] + \
+    [(m, tgs, "stairs", org) for m in HF.STAIRS_MODELS for tgs in (False, True) for org in (False, True)]
+
+
+def test_stairs_field_is_the_tasks_stairs():
+    f = HF.stairs_field()
+    assert f.H.shape == (65, 65) and f.dx == float(np.float32(0.1)) and f.H.max() > 1.0
+    d = np.diff(f.H.astype(np.float64), axis=0)
+    assert set(np.round(np.unique(d), 6)) == {-0.15, 0.0, 0.15}      # one-cell ramps of gradient 1.5: |n.x| = 0.83
+    _, n, _ = HF.facet(f, -3.2 + 0.1 * np.array([2.3, 2.3]), np.array([0.02, 0.0]))
+    assert np.abs(n[:, 0]).max() >= HF.STEEP
+
+
+@pytest.mark.parametrize("model,tgs,kind,origins", ROUGH)
+def test_rough_ground_steps_are_admitted(model, tgs, kind, origins):
+    """the conditions of a rough_case, on the oracle alone.  Measured: DESIGN.md §15"""
+    c = HF.rough_case(model, tgs, kind, origins)
+    spec, mnp, sp = c["spec"], c["mnp"], c["sp"]
+    want = max(LF.BATCHES[model])
+    assert sp.substeps == 2 and len(c["idx"]) == want and c["cand"] <= sp.max_contacts
+    assert (c["fld"].origins is not None) == origins
+    if model == "T16-free":
+        assert len(spec.pairs) > 0       # with its self-collision pairs
+    passed_over = c["scanned"] - want
+    multi, sx, sy = HF.row_stats(c)
+    mv = HF.moved(spec, c["ref"], c["level"], want)
+    print(f"{model} {kind} tgs={tgs} origins={origins}: scanned {c['scanned']}, passed over {passed_over} {c['why']}, "
+          f"two or more facets {multi.mean():.2f}, steep along x {sx.mean():.2f}, along y {sy.mean():.2f}, "
+          f"moved against the level step {mv.mean():.2f}")
+    assert passed_over <= LF.DISCARD_CAP * c["scanned"], f"{passed_over} of {c['scanned']} drawn states passed over"
+    assert multi.sum() >= 0.5 * want, "the case is only a slope case"
+    if kind == "stairs":
+        assert sx.sum() >= 0.1 * want and sy.sum() >= 0.1 * want
+    assert mv.sum() >= 0.9 * want
+    # inside the grid
+    xy = c["root"][:, 0:2] + (c["fld"].origins[:, 0:2] if origins else 0)
+    assert np.abs(xy).max() < 0.5 * (c["fld"].nx - 1) * c["fld"].dx
+    twin = HF.field_step(c["fld"], LF.Host(spec, c["root"], c["dof"], c["act"], c["tgt"]), mnp, sp, fp32=True)
+    HF.compare_step(f"test_rough_ground_steps_are_admitted[{model}-{tgs}-{kind}-{origins}]", spec, twin, c["ref"], want)
+
+
+@pytest.mark.parametrize("model,tgs", [(m, tgs) for m in ("T16-free", "Anymal") for tgs in (False, True)])
+def test_chained_launches_are_admitted(model, tgs):
+    """four launches on the rough field, each from the last one's output, with the oracle's fp32 twin in the kernel's
+    place: per launch at most 5 % of the states fail the admission, and the twin passes the one-step rule on the rest"""
+    c = HF.rough_case(model, tgs)
+    chain = HF.chain_case(model, tgs)
+    assert len(chain) == 4
+    for k, (inp, ref, ok) in enumerate(chain):
+        n = inp.n
+        print(f"{model} tgs={tgs} launch {k}: {int((~ok).sum())} of {n} states not admitted")
+        assert (~ok).sum() <= LF.DISCARD_CAP * n
+        twin = HF.field_step(c["fld"], LF.Host(c["spec"], inp.root, inp.dof, c["act"], c["tgt"]), c["mnp"], c["sp"], fp32=True)
+        keep = np.flatnonzero(ok)
+        HF.compare_step(f"test_chained_launches_are_admitted[{model}-{tgs}-{k}]", c["spec"], HF.take(twin, keep),
+                        HF.take(ref, keep), len(keep))
+        if k:
+            assert np.abs(inp.root - chain[k - 1][0].root).max() > 1e-5     # the chain moves
+
+
+@pytest.mark.parametrize("origins", [False, True], ids=["world", "origins"])
+def test_terrain_physics_case_is_admitted(origins):
+    """AnymalTerrain's physics on a generated terrain, the oracle's fp32 twin in the kernel's place: four launches, the
+    efforts recomputed by the restatement's PD law before each, each compared with the fp64 oracle restarted from the
+    same state -- the rule and the 5 % cap of the GPU test -- and the placement is what it says"""
+    import types
+    import anymal_terrain_ref as R
+    c = HF.terrain_case(origins)
+    n, fld = c["n"], c["fld"]
+    assert fld.H.shape == (560, 800) and sorted(set(c["col"])) == sorted(HF.TERRAIN_COLS)
+    xy = c["root"][:, 0:2] + (fld.origins[:, 0:2] if origins else 0)
+    _, nrm, _ = HF.facet(fld, xy[:, 0], xy[:, 1])
+    assert (np.abs(c["root"][:, 0:2]).max() < 4.0) == origins
+    root, dof = c["root"], c["dof"]
+    steep = 0
+    for k in range(4):
+        _, eff = R.pre_step(c["p"], c["actions"], dof)
+        twin = HF.field_step(fld, LF.Host(c["spec"], root, dof, eff), c["mnp"], c["sp"], fp32=True)
+        got = types.SimpleNamespace(root=twin.root, dof=twin.dof, ncf=twin.ncf)
+        HF.terrain_compare(f"test_terrain_physics_case_is_admitted[{origins}-launch {k}]", c, got, root, dof, eff)
+        rows = HF.field_rows(fld, LF.Host(c["spec"], root, dof, eff), c["mnp"], c["sp"])
+        steep += sum(bool((np.abs(r[(r[:, 3] == -1) & (r[:, 11] > 1e-9)][:, 7:9]) >= HF.STEEP).any()) for r in rows)
+        root, dof = twin.root, twin.dof
+    print(f"origins={origins}: {steep} env-launches use a ground row with |n.x| or |n.y| >= {HF.STEEP}")
+    assert steep >= 4
 
 
 def test_scan_points_outside_the_rounding_band():
